@@ -8,13 +8,15 @@ One step = the BASELINE.json configs[1] + configs[2] workload on one batch held 
 Cauchy matrix (bit-exact with module/rs.c).  Weak scaling: every rank owns its own
 100 000 groups (distinct seeds); value = all ranks' data bytes / the slowest rank's time.
 
-Beside the headline, every rank also runs (inside barriers, max-over-ranks timing):
+Beside the headline, with --full every rank also runs (inside barriers, max-over-ranks timing):
   config4     RS(16,4) encode + 4-erasure reconstruct of 250 000 x 1400 B groups, split
               contiguously over the ranks (strong scaling: the job is fixed), and
   host_mixed  config 5: mixed (4,2)/(10,3)/(16,4) batches streamed host -> device -> host
               through the qfec_pipe engine (pinned buffers, 3 HIP streams per GPU).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+      a plain run sets up, warms up, times the K steps and prints the line; --full adds the
+      legs described above, the calibration probes and the CPU baselines to it.
       --gpus N > 1 without WORLD_SIZE: this process starts N rank processes itself (before
       any GPU call) and exits with the worst of their return codes.
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, the same protocol)
@@ -73,6 +75,12 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); >1 without WORLD_SIZE spawns them")
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline, run every other leg: calibration probes, config 4, the host-to-host, "
+                        "per-call, side, wire and zfec legs and the CPU baselines (each still has its --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed to DIR/parity.npy and "
+                        "DIR/restored.npy (float32; a fixed, seeded sample of the groups, under 64 MB in all)")
     p.add_argument("--spinup-ms", type=float, default=25.0,
                    help="setup: run the step for this long before the W warmup steps (clock ramp, tools/sustain.py)")
     p.add_argument("--k", type=int, default=10)
@@ -996,6 +1004,26 @@ def kernel_sources_hash(sources=KERNEL_SOURCES):
     return h.hexdigest()[:16]
 
 
+DUMP_SEED = 0x5EED00D0
+DUMP_BUDGET = 60_000_000  # bytes of float32 over both arrays (the files stay under 64 MB in all)
+
+
+def dump_outputs(path, parity, work, rank, world):
+    """--dump-outputs: what the timed path's last step left in its two output buffers -- the
+    parity rows encode wrote and the data rows reconstruct restored -- for a fixed, seeded
+    sample of the groups (every group when they fit the budget), as float32 <name>.npy
+    (<name>.rank<r>.npy at more than one rank)."""
+    G = parity.shape[0]
+    per_group = (parity[0].numel() + work[0].numel()) * 4
+    S = max(1, min(G, DUMP_BUDGET // world // per_group))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(G, size=S, replace=False))
+    sel = torch.from_numpy(idx).to(parity.device)
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+    for name, t in (("parity", parity), ("restored", work)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), t.index_select(0, sel).cpu().numpy().astype(np.float32))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -1008,6 +1036,8 @@ def main(argv=None):
             import torch.distributed as dist
             dist.destroy_process_group()
         return rc
+    if not args.full:  # a plain run: the headline's timed steps alone
+        args.no_cpu = args.no_side = args.no_config4 = args.no_host = True
     qa.set_kernel_variant(args.variant)
     if args.config4_only:  # measurement helper: the config 4 leg's launches alone, under a profiler
         c4 = config4_sharded(rank, world, args.config4_groups, steps=args.steps, warmup=args.warmup)
@@ -1072,6 +1102,8 @@ def main(argv=None):
     # correctness guard on the measured buffers: reconstruct restored the data exactly
     ok = bool(torch.equal(work, data))
     ok = all_sum(0.0 if ok else 1.0, world) == 0.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, parity, work, rank, world)
 
     data_bytes_rank = (G + dec_groups) * k * B * args.steps
     total_bytes = all_sum(float(data_bytes_rank), world)
@@ -1097,7 +1129,7 @@ def main(argv=None):
 
     # calibration probe: the encode's traffic with XOR only (not a codec)
     probe_ms = copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         scratch = torch.empty_like(parity)
         for _ in range(3):

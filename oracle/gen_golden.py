@@ -530,7 +530,9 @@ def gen_wire():
         out[f"parsed_{key}"] = parsed
         out[f"shards_{key}"] = shards
         out[f"srcinfo_{key}"] = srcinfo
-    np.savez_compressed(os.path.join(OUT, "wire.npz"), **out)
+    for c in (0, 1):  # one file per checksum setting (each stays under 1 MiB)
+        np.savez_compressed(os.path.join(OUT, f"wire_c{c}.npz"),
+                            **{key: v for key, v in out.items() if key.endswith(f"_{c}")})
 
 
 def main():

@@ -68,7 +68,7 @@ def test_launcher_refuses_more_ranks_than_gpus():
 
 def test_rccl_path_one_rank():
     """The RCCL branch of dist_setup and the device-tensor reductions, on hardware, at 1 rank."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--force-dist", "--full", "--steps", "5", "--warmup", "2",
                         "--no-cpu", "--no-side", "--no-host", "--config4-groups", "20000"],
                        capture_output=True, text=True, timeout=300,
                        env=_env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",

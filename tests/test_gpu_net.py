@@ -1,7 +1,7 @@
 """GPU tests of the batched NetFecCodec layer (include/qfec_net.h, quicknet_amd.NetFec):
 sessions keep zfec_pack_input's numbering (network/NetFecCodec.cpp:68-175) and the wire bytes
 equal the oracle's restatement of the per-packet path (itself pinned to the reference's
-FecCodecBuf.cpp by tests/golden/wire.npz); the receive side delivers exactly the packets
+FecCodecBuf.cpp by tests/golden/wire_c*.npz); the receive side delivers exactly the packets
 zfec_unpack_input would (every source packet of a decodable group, else the received valid
 ones), with their source indices."""
 import numpy as np

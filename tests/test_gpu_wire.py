@@ -1,5 +1,5 @@
 """GPU parity of the FEC datagram batch kernels (quicknet_amd/csrc/qfec_wire.hip) against the
-wire vectors the reference's own network/FecCodecBuf.cpp produced (tests/golden/wire.npz)
+wire vectors the reference's own network/FecCodecBuf.cpp produced (tests/golden/wire_c*.npz)
 and against the oracle at larger sizes.  Bit-exact."""
 import numpy as np
 import pytest
@@ -52,7 +52,7 @@ def wire_pitch_for(shard_pitch, align):
 @pytest.mark.parametrize("k,n", WIRE)
 @pytest.mark.parametrize("checksum", [1, 0])
 def test_pack_vs_reference(golden, wire_fused, wire_align, k, n, checksum):
-    z = golden("wire.npz")
+    z = golden(f"wire_c{checksum}.npz")
     key = f"{k}_{n}_{checksum}"
     sizes, payload, seq = z[f"sizes_{key}"], z[f"payload_{key}"], z[f"seq_{key}"]
     dg, dl = z[f"dgrams_{key}"], z[f"dlen_{key}"]
@@ -74,7 +74,7 @@ def test_pack_vs_reference(golden, wire_fused, wire_align, k, n, checksum):
 @pytest.mark.parametrize("k,n", WIRE)
 @pytest.mark.parametrize("checksum", [1, 0])
 def test_unpack_vs_reference(golden, wire_fused, k, n, checksum):
-    z = golden("wire.npz")
+    z = golden(f"wire_c{checksum}.npz")
     key = f"{k}_{n}_{checksum}"
     dg, dl = z[f"dgrams_{key}"], z[f"dlen_{key}"]
     parsed, shards_ref, srcinfo = z[f"parsed_{key}"], z[f"shards_{key}"], z[f"srcinfo_{key}"]

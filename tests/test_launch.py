@@ -20,6 +20,15 @@ def _env(**extra):
     return env
 
 
+def _fake_env(root, **extra):
+    """The environment for a launcher that reads the fake topology under `root`: the host's own
+    device-visibility filters name its real GPUs, not the fake tree's, so they are left out."""
+    env = {k: v for k, v in _env(**extra).items()
+           if k not in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    env["QFEC_SYSFS_ROOT"] = root
+    return env
+
+
 def _run(args, env=None, timeout=180):
     return subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, timeout=timeout,
                           env=env or _env(), cwd=ROOT)
@@ -121,7 +130,7 @@ def test_launch_check_parent_is_gpu_free(tmp_path):
     """The launcher's pre-spawn state: torch never imported, no /dev/kfd or /dev/dri fd open,
     devices counted from sysfs, a NUMA plan per rank."""
     root = _fake_sysfs(str(tmp_path), GPUS)
-    r = _run(["--gpus", "3", "--launch-check"], env=_env(QFEC_BENCH_BACKEND="nccl", QFEC_SYSFS_ROOT=root))
+    r = _run(["--gpus", "3", "--launch-check"], env=_fake_env(root, QFEC_BENCH_BACKEND="nccl"))
     assert r.returncode == 0, r.stderr[-2000:]
     out = _line(r.stdout)
     assert out["torch_imported"] is False and out["gpu_fds"] == []
@@ -133,7 +142,7 @@ def test_launcher_refuses_missing_gpus(tmp_path):
     """Counted from sysfs: more ranks than visible GPUs exits 2 before starting anything."""
     root = _fake_sysfs(str(tmp_path), GPUS)
     t0 = time.time()
-    r = _run(["--gpus", "4"], env=_env(QFEC_BENCH_BACKEND="nccl", QFEC_SYSFS_ROOT=root))
+    r = _run(["--gpus", "4"], env=_fake_env(root, QFEC_BENCH_BACKEND="nccl"))
     assert r.returncode == 2
     assert "only 3 GPU(s) visible" in r.stderr
     assert time.time() - t0 < 30
@@ -142,7 +151,8 @@ def test_launcher_refuses_missing_gpus(tmp_path):
 def test_ranks_check_their_own_device_when_sysfs_is_silent(tmp_path):
     """No readable topology: the launcher starts the ranks and each checks its own index
     (this container has no GPU), so the job exits 2 instead of running on nothing."""
-    r = _run(["--gpus", "2", "--no-cpu"], env=_env(QFEC_BENCH_BACKEND="nccl", QFEC_SYSFS_ROOT=str(tmp_path)))
+    r = _run(["--gpus", "2", "--no-cpu", "--fail-grace-s", "2"],
+             env=_env(QFEC_BENCH_BACKEND="nccl", QFEC_SYSFS_ROOT=str(tmp_path)))
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
     assert "GPU(s) are visible" in r.stderr
 

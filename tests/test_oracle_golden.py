@@ -171,7 +171,7 @@ WIRE = [(4, 5), (4, 6), (3, 5), (5, 8), (7, 8), (10, 13), (2, 4), (3, 4), (14, 1
 def test_wire_pack_unpack(oracle, golden, k, n, checksum):
     """The FEC wire format vs the reference's own FecCodecBuf.cpp (send: set_fec_enc_buf,
     get_fec_encoded_pkt, pack_fec_head; receive: unpack_fec_head, dec_src_pkt_info)."""
-    z = golden("wire.npz")
+    z = golden(f"wire_c{checksum}.npz")
     key = f"{k}_{n}_{checksum}"
     sizes, payload, seq = z[f"sizes_{key}"], z[f"payload_{key}"], z[f"seq_{key}"]
     dg, dl, gmax = z[f"dgrams_{key}"], z[f"dlen_{key}"], z[f"gmax_{key}"]

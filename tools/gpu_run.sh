@@ -6,15 +6,15 @@
 #   tests EXPR            python -m pytest tests -m gpu -k EXPR (EXPR "all": the whole GPU suite)
 #   ab K M B G ONLY [ARGS...]
 #                         tools/ab.py interleaved A/B (ONLY: comma-separated variant prefixes)
-#   bench [ARGS...]       bench.py -> TAG/bench.json (stderr TAG/bench.err)
-#   kstats [ARGS...]      rocprofv3 --kernel-trace --stats over bench.py --no-cpu --no-host --no-side -> TAG/prof/,
+#   bench [ARGS...]       bench.py --full -> TAG/bench.json (stderr TAG/bench.err)
+#   kstats [ARGS...]      rocprofv3 --kernel-trace --stats over bench.py --full --no-cpu --no-host --no-side -> TAG/prof/,
 #                         summary TAG/kernel_stats.csv
 #   pmc NAME K M B G [ARGS...]
 #                         tools/pmc_traffic.py (separate --pmc passes per counter group) -> TAG/traffic_NAME.json
 #   sq NAME SCRIPT [ARGS...]
 #                         SQ counters per kernel (two --pmc passes over python SCRIPT) -> TAG/NAME_sq_summary.txt
 #   smoke                 __graft_entry__.smoke()
-#   bench2                bench.py --gpus 2 with gloo (the launcher's two ranks share the one GPU) -> TAG/bench_g2.json
+#   bench2                bench.py --full --gpus 2 with gloo (the launcher's two ranks share the one GPU) -> TAG/bench_g2.json
 #   wirestats             rocprofv3 kernel stats of the datagram kernels at the wire leg's shapes -> TAG/wire_kernel_stats.csv
 #   merge_traffic         the TAG/traffic_*.json entries of earlier pmc steps into profiles/traffic.json (on the box,
 #                         so a later bench step reads them; copy it back from TAG/traffic.json)
@@ -56,7 +56,7 @@ for spec in "${specs[@]}"; do
       tail -30 $OUT/ab_${k}_${m}_${b}_${g}_$n.log ;;
     bench)
       echo "== bench"
-      timeout -k 10 400 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 400 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "   rc=$rc"; cat $OUT/bench.json
       if [ $rc -ne 0 ]; then tail -30 $OUT/bench.err; exit $rc; fi ;;
     kstats)
@@ -64,7 +64,7 @@ for spec in "${specs[@]}"; do
       # only the timed step's launches and config 4's (the host / per-call / side legs launch the same
       # kernels at other sizes), so each kernel's average is the one bench.py reports
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-        python3 bench.py --no-cpu --no-host --no-side "$@" > $OUT/kstats.log 2>&1
+        python3 bench.py --full --no-cpu --no-host --no-side "$@" > $OUT/kstats.log 2>&1
       rc=$?; echo "   rc=$rc"; tail -3 $OUT/kstats.log
       if [ $rc -ne 0 ]; then exit $rc; fi
       f=$(find $OUT/prof -name '*kernel_stats.csv' | head -1)
@@ -92,7 +92,7 @@ for spec in "${specs[@]}"; do
       cat $OUT/${name}_sq_summary.txt ;;
     bench2)
       echo "== bench --gpus 2 (gloo)"
-      QFEC_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 20 --no-cpu > $OUT/bench_g2.json 2> $OUT/bench_g2.err
+      QFEC_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --no-cpu > $OUT/bench_g2.json 2> $OUT/bench_g2.err
       rc=$?; echo "   rc=$rc"; cut -c1-400 $OUT/bench_g2.json
       if [ $rc -ne 0 ]; then tail -20 $OUT/bench_g2.err; exit $rc; fi ;;
     wirestats)

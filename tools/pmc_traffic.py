@@ -30,7 +30,7 @@ WIRE_KERNELS = {"pack": "k_pack_wave64<10, 3, 1, 0, 1, 16, 0>", "unpack": "k_rx<
 def run_pass(counter, out, bench_args, k, m, kernels=KERNELS, script="bench.py"):
     d = os.path.abspath(os.path.join(out, counter.lower()))
     os.makedirs(d, exist_ok=True)
-    extra = ["--no-cpu"] if script == "bench.py" else []
+    extra = ["--full", "--no-cpu"] if script == "bench.py" else []
     cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", counter.lower(), "--",
            sys.executable, os.path.join(ROOT, script)] + extra + bench_args
     env = dict(os.environ, TMPDIR="/tmp")
