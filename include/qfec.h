@@ -124,6 +124,51 @@ int qfec_prepare_reconstruct(qfec_code *code);
 int qfec_decode_rows(const qfec_code *code, const unsigned char *marks_n,
                      unsigned char *rows_out, int *survivors_out, int *erased_out);
 
+/* Bring every group back to full strength in one launch: rewrite every marked shard, data AND
+ * parity, from the k lowest unmarked shards (all surviving data, then the first e surviving parity
+ * rows -- the set qfec_reconstruct uses; all of the data when no data shard is marked).  Layouts,
+ * marks, pitch, stream and the scratch bytes in [block_size, round_up(block_size, 16)) are exactly
+ * as for qfec_reconstruct; the one difference is that d_parity is written.  Per group, with t
+ * marked shards of which e are data:
+ *   t = 0   untouched.
+ *   t > m   under-determined (e <= surviving parity holds exactly when t <= m): untouched and
+ *           counted into *d_failed (device counter, may be NULL; accumulated, not reset).
+ *   else    every marked data row is rewritten byte for byte as qfec_reconstruct rewrites it (the
+ *           same decode rows, rs.c's stale-row quirk included); every marked parity row j becomes
+ *           rows[j] x [identity on surviving data; the decode rows on erased data] applied to the
+ *           survivors -- a true GF product, no stale-row semantics.
+ * A repaired parity row equals what qfec_encode writes into it from the repaired data whenever no
+ * quirk-stale coefficient is involved (a zero column-0 coefficient of that parity row or of a
+ * decode row, with rs_stale_quirk = 1).  Codes from qfec_code_new have none, so there it always
+ * does; codes with edited or explicit rows may differ in exactly those rows.
+ * No other byte of data or parity is written.  Always the perm-table kernels
+ * (qfec_set_kernel_variant does not apply).  Asynchronous on `stream`; the pattern -> rows LUT
+ * (2^(k+m) entries, keyed by the whole mask) is built on the first call or by qfec_prepare_repair.
+ * k + m > 24 returns QFEC_EUNSUP: there is no host-record path for repair. */
+int qfec_repair(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                const unsigned char *d_marks, long long groups, int block_size,
+                long long pitch, unsigned int *d_failed, void *stream);
+int qfec_prepare_repair(qfec_code *code);
+
+/* Host-side repair-matrix query for one group (group-order marks[n]): t <= m rows of k coefficients
+ * over the survivors listed in survivors[k] (the k lowest unmarked ids), one row per marked shard
+ * in lost[t] (ids 0..n-1 ascending: data rows first, then parity rows k + j).  Returns t, 0 when
+ * nothing is marked, or -1 when under-determined.  Any k + m.  CPU only, like qfec_decode_rows. */
+int qfec_repair_rows(const qfec_code *code, const unsigned char *marks_n,
+                     unsigned char *rows_out /* t*k */, int *survivors_out /* k */,
+                     int *lost_out /* t */);
+
+/* Does the parity match the data?  Bit j of d_bad_rows[g] is set iff parity row j of group g
+ * differs from rows[j] x data[g] (a true GF product) in any byte of [0, block_size); 0 = the group
+ * is consistent.  d_bad_rows ([groups], may be NULL) is written for every group; *d_bad_groups
+ * (device counter, may be NULL; accumulated, not reset) gains 1 per group with any bad row.  Bytes
+ * in [block_size, pitch) of either buffer never influence the result.  Reads (k + m) rows per
+ * group, writes nothing else; asynchronous on `stream`.  m > 32 returns QFEC_EUNSUP. */
+int qfec_verify(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                long long groups, int block_size, long long pitch,
+                unsigned int *d_bad_rows /* [groups], nullable */,
+                unsigned int *d_bad_groups /* counter, accumulates, nullable */, void *stream);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

@@ -271,6 +271,55 @@ class Code:
                                      _dev_ptr(marks, what="marks"), G, block_size, pitch,
                                      _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_reconstruct")
 
+    def prepare_repair(self):
+        check(lib().qfec_prepare_repair(self._h), "qfec_prepare_repair")
+
+    def repair(self, data, parity, marks, block_size=None, failed=None, stream=None):
+        """Rewrite every marked shard, data and parity, in place (qfec_repair).  data uint8
+        [G, k, pitch], parity uint8 [G, m, pitch], marks uint8 [G*k + G*m] (rs.c layout) on device;
+        failed: optional device int32/uint32 [1] counter of under-determined groups (t > m)."""
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch) or marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
+                            f"marks {marks.numel()} for ({self.k},{self.m})")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_repair(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_repair")
+
+    def repair_rows(self, marks_n):
+        """Host-side repair matrix for one group-order mark vector over all n shards:
+        (t, rows[t,k], survivors[k], lost[t]); t = 0 nothing marked, -1 under-determined."""
+        marks_n = np.ascontiguousarray(marks_n, dtype=np.uint8)
+        if marks_n.size != self.k + self.m:
+            raise QfecError(f"repair_rows: {marks_n.size} marks for ({self.k},{self.m})")
+        rows = np.zeros((max(self.m, 1), self.k), dtype=np.uint8)
+        surv = np.zeros(self.k, dtype=np.int32)
+        lost = np.zeros(max(self.m, 1), dtype=np.int32)
+        t = lib().qfec_repair_rows(self._h, marks_n.ctypes.data, rows.ctypes.data, surv.ctypes.data, lost.ctypes.data)
+        if t <= 0:
+            return t, None, None, None
+        return t, rows[:t].copy(), surv, lost[:t].copy()
+
+    def verify(self, data, parity, block_size=None, bad_rows=None, bad_groups=None, stream=None):
+        """Does parity[g] equal P x data[g] (qfec_verify)?  Returns bad_rows, a device int32 [G]
+        tensor (allocated when not given): bit j set = parity row j of that group differs in some
+        byte of [0, block_size); bad_groups: optional device int32/uint32 [1] counter that gains 1
+        per inconsistent group (accumulates)."""
+        import torch
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
+        if bad_rows is None:
+            bad_rows = torch.empty(G, dtype=torch.int32, device=data.device)
+        elif bad_rows.numel() != G:
+            raise QfecError(f"verify: bad_rows has {bad_rows.numel()} elements for {G} groups")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_verify(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
+                                pitch, _dev_ptr(bad_rows, _I32, "bad_rows"), _dev_ptr(bad_groups, _I32, "bad_groups"),
+                                _stream_handle(stream)), "qfec_verify")
+        return bad_rows
+
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15
     def pack_datagrams(self, payload, offsets, sizes, seq, checksum=True, shard_pitch=None, wire_pitch=None,
                        stream=None):

@@ -247,6 +247,63 @@ int decode_rows(const uint8_t* P, int k, int m, const uint8_t* marks, std::vecto
     return e;
 }
 
+int repair_rows(const uint8_t* P, int k, int m, const uint8_t* marks, std::vector<uint8_t>& rows,
+                std::vector<int>& survivors, std::vector<int>& lost, const uint8_t* full, int* e_out) {
+    const int n = k + m;
+    int t = 0;
+    for (int i = 0; i < n; ++i) t += marks[i] ? 1 : 0;
+    rows.clear();
+    survivors.clear();
+    lost.clear();
+    if (e_out) *e_out = 0;
+    if (t == 0) return 0;
+    if (t > m) return -1;  // e <= surviving parity holds exactly when t <= m
+    std::vector<uint8_t> drows;
+    std::vector<int> dlost;
+    // e == 0 leaves survivors = every data shard, which is the k lowest unmarked ids then too
+    const int e = decode_rows(P, k, m, marks, drows, survivors, dlost, full);
+    if (e < 0) return -1;
+    if (e_out) *e_out = e;
+    lost = dlost;
+    for (int j = 0; j < m; ++j)
+        if (marks[k + j]) lost.push_back(k + j);
+    rows.assign((size_t)t * k, 0);
+    if (e) memcpy(rows.data(), drows.data(), (size_t)e * k);
+    const Field& f = field();
+    std::vector<int> pos((size_t)k, -1);  // column of a surviving data shard among the survivors
+    for (int c = 0; c < k; ++c)
+        if (survivors[c] < k) pos[survivors[c]] = c;
+    for (int r = e; r < t; ++r) {
+        const uint8_t* pr = P + (size_t)(lost[r] - k) * k;
+        uint8_t* out = &rows[(size_t)r * k];
+        for (int i = 0; i < k; ++i)
+            if (pos[i] >= 0) out[pos[i]] ^= pr[i];
+        for (int j = 0; j < e; ++j) {
+            const uint8_t q = pr[dlost[j]];
+            if (!q) continue;
+            const uint8_t* mq = f.mul[q];
+            for (int c = 0; c < k; ++c) out[c] ^= mq[drows[(size_t)j * k + c]];
+        }
+    }
+    return t;
+}
+
+void build_repair_record(const RecordLayout& L, int k, int t, int e, const uint8_t* rows, const int* survivors,
+                         const int* lost, bool rs_quirk, uint32_t* out) {
+    memset(out, 0, (size_t)L.hdr * sizeof(uint32_t));
+    out[0] = (uint32_t)t;
+    out[2] = (uint32_t)e;
+    for (int c = 0; c < k; ++c) out[L.surv_off + c] = (uint32_t)survivors[c];
+    for (int j = 0; j < t; ++j) out[L.lost_off + j] = (uint32_t)lost[j];
+    for (int j = 0; j < t; ++j)
+        for (int c = 0; c < k; ++c) out[L.coff + j * k + c] = (uint32_t)rows[(size_t)j * k + c] * (QFEC_TAB_STRIDE * 4);
+    // the rs.c stale-row quirk belongs to the data rows alone (module/rs.c:116-117 as the
+    // reconstruct applies it); a repaired parity row is a true product
+    if (rs_quirk)
+        for (int j = 0; j < e && j < 32; ++j)
+            if (rows[(size_t)j * k] == 0) out[1] |= 1u << j;
+}
+
 RecordLayout record_layout(int k, int m) {
     RecordLayout L;
     L.surv_off = 4;

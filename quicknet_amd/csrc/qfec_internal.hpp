@@ -75,6 +75,43 @@ struct ReconArgs {
     int rlds;                 // reconstruct skeleton probe: LDS bytes per block, a residency cap (0 none)
 };
 
+// group repair (qfec_kernels.hip, "repair"): every marked shard of a group, data or parity
+struct RepairArgs {
+    uint8_t* data;            // [groups][k][pitch]
+    uint8_t* parity;          // [groups][m][pitch]
+    const uint8_t* dmarks;    // [groups][k] data marks of this launch's groups
+    const uint8_t* pmarks;    // [groups][m] parity marks of this launch's groups
+    const int32_t* lut;       // [2^n] full n-bit mask -> record offset (dwords) / QFEC_REC_*
+    const uint32_t* records;  // compact repair records (RecordLayout header only, no inline tables)
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    unsigned int* failed;
+    uint64_t groups;
+    uint64_t pitch;
+    uint64_t dgs, pgs;        // bytes between groups: data rows, parity rows
+    uint32_t cols;            // 16-B columns (vec16) or bytes per row
+    uint32_t cols8, wpg8;     // 8-B columns per row and waves per group at 64 of them per wave
+    int k, m;
+    int surv_off, lost_off, coff;
+    int vec16;
+};
+
+// batched parity check (qfec_verify.hip): the encode's mapping, compares in place of the stores
+struct VerifyArgs {
+    const uint8_t* data;      // [groups][k][pitch]
+    const uint8_t* parity;    // [groups][m][pitch]
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    unsigned int* bad_rows;   // [groups] of this launch, zeroed before it; bit j = parity row j differs
+    unsigned int* bad_groups; // counter of groups with any bad row; may be NULL
+    uint64_t work;            // groups * cols lanes (< 2^31)
+    uint64_t pitch;
+    uint64_t dgs, pgs;
+    DivMagic cols_div;
+    uint32_t cols;            // 16-B columns (vec16) or bytes per row
+    uint32_t block;           // block_size: bytes of a row that count
+    int k, m;
+    int vec16;
+};
+
 // FEC datagram batches (qfec_wire.hip): shards[G][n][pitch], wire[G][n][wire_pitch]
 struct WireArgs {
     const uint8_t* payload;   // send: concatenated payloads (16 readable bytes past the last)
@@ -162,6 +199,8 @@ Tuning& tuning();
 
 hipError_t launch_encode(const EncodeArgs& a, int variant, hipStream_t stream);
 hipError_t launch_reconstruct(const ReconArgs& a, hipStream_t stream);
+hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
+hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);
@@ -209,6 +248,21 @@ struct RecordLayout {
     size_t words(int e, int k) const { return (size_t)hdr + (size_t)e * k * QFEC_TAB_STRIDE; }
 };
 RecordLayout record_layout(int k, int m);
+
+// repair rows of one erasure pattern over all n = k + m shards (group-order marks).  Returns t =
+// the number of marked shards (1..m), 0 if nothing is marked or -1 if t > m (under-determined; also
+// when the decode matrix is singular).  On t >= 1: survivors (k) = the k lowest unmarked ids, lost
+// (t) = the marked ids ascending (data first), rows (t x k) over the survivors: the decode rows of
+// decode_rows for the e erased data shards, then for every marked parity row j
+// P[j] x [identity on surviving data; those decode rows on erased data] -- a true GF product.
+// *e_out (nullable) = e.  `full` as in decode_rows.
+int repair_rows(const uint8_t* parity_rows, int k, int m, const uint8_t* marks_n, std::vector<uint8_t>& rows,
+                std::vector<int>& survivors, std::vector<int>& lost, const uint8_t* full = nullptr,
+                int* e_out = nullptr);
+// compact repair record: the RecordLayout header alone (hdr words): [0] t, [1] rs.c quirk flags of
+// the e data rows, [2] e, survivors, lost ids (0..n-1), coefficient-table byte offsets
+void build_repair_record(const RecordLayout& L, int k, int t, int e, const uint8_t* rows, const int* survivors,
+                         const int* lost, bool rs_quirk, uint32_t* out);
 void build_record(const RecordLayout& L, int k, int e, const uint8_t* rows, const int* survivors,
                   const int* lost, bool rs_quirk, uint32_t* out);
 

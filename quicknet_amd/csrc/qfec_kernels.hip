@@ -5,6 +5,8 @@
 //                  module/rs.c:364-378 (code_some_shards), module/fec.c:714-733 (fec_encode)
 //   reconstruct  data[g][lost_r][b] = XOR_s D_pat[r][s] * survivor[g][s][b]
 //                  module/rs.c:500-643, module/fec.c:821-862
+//   repair       reconstruct, plus parity[g][lost_j][b] = XOR_s R_pat[j][s] * survivor[g][s][b] for
+//                  every lost parity row, in the same pass (no counterpart in the reference)
 // GF(2^8) over x^8+x^4+x^3+x^2+1 (0x11D).  No floating point, no MFMA: this is byte-wise
 // Galois arithmetic, HBM-bound.
 //
@@ -538,6 +540,185 @@ __global__ void __launch_bounds__(256) k_reconstruct_any(ReconArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ repair
+// Every marked shard of a group, data or parity, in one pass: the k lowest unmarked shards are read
+// once and the t marked rows written.  The full n-bit mask indexes a LUT of its own to a compact
+// record (RecordLayout header only): [0] t, [1] quirk flags of the data rows, [surv_off + c]
+// survivor id, [lost_off + j] marked id (0..n-1, ascending), [coff + j*k + c] table byte offset in
+// the 256-entry table.  The rows of marked data shards are the reconstruct's decode rows; the row of
+// a marked parity shard j is P[j] x [identity on surviving data; decode rows on erased data]
+// (gf256.cpp repair_rows).  Mapping as the reconstruct's auto body: 8-B lanes, one wave per 64
+// columns of a group, one group per block where a group is at most 4 waves.
+
+template <int K, int T, int D>
+__device__ __forceinline__ void repair_column_t(const uint8_t* const (&src)[K], uint8_t* __restrict__ data_g,
+                                                uint8_t* __restrict__ par_g, uint64_t lost_bits, const RTab& R,
+                                                uint64_t pitch, uint64_t off) {
+    uint32_t x[K][D];
+#pragma unroll
+    for (int c = 0; c < K; ++c) ldv<D>(x[c], src[c] + off);
+    uint8_t* dst[T];
+    uint32_t acc[T][D];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(lost_bits);
+        lost_bits &= lost_bits - 1;
+        dst[j] = (l < (uint32_t)K ? data_g + (uint64_t)l * pitch : par_g + (uint64_t)(l - K) * pitch) + off;
+#pragma unroll
+        for (int d = 0; d < D; ++d) acc[j][d] = 0;
+        if (R.quirk(j, K)) ldv_plain<D>(acc[j], dst[j]);  // rs.c column-0 quirk (data rows only)
+    }
+    recon_mac_core<K, T, D>(x, acc, R);
+#pragma unroll
+    for (int j = 0; j < T; ++j) stv<D>(dst[j], acc[j]);
+}
+
+// wave-uniform dispatch on t to the exact-row-count body
+template <int K, int M, int D, int T = M>
+__device__ __forceinline__ void repair_column_by_t(const uint8_t* const (&src)[K], uint8_t* __restrict__ data_g,
+                                                   uint8_t* __restrict__ par_g, uint64_t lost_bits, const RTab& R,
+                                                   int t, uint64_t pitch, uint64_t off) {
+    if constexpr (T > 1) {
+        if (t < T) {
+            repair_column_by_t<K, M, D, T - 1>(src, data_g, par_g, lost_bits, R, t, pitch, off);
+            return;
+        }
+    }
+    repair_column_t<K, T, D>(src, data_g, par_g, lost_bits, R, pitch, off);
+}
+
+// ONE: one group per block of wpg8 waves (wpg8 <= 4), else 4 waves per block over (group, slab)
+template <int K, int M, bool ONE>
+__global__ void __launch_bounds__(256) k_repair_perm(RepairArgs a, uint8_t* __restrict__ data,
+                                                     uint8_t* __restrict__ parity,
+                                                     const uint8_t* __restrict__ dmarks,
+                                                     const uint8_t* __restrict__ pmarks,
+                                                     const int32_t* __restrict__ lut,
+                                                     const uint32_t* __restrict__ records) {
+    constexpr int N = K + M;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint64_t g;
+    uint32_t part;
+    if (ONE) {
+        g = blockIdx.x;
+        part = wave;
+    } else {
+        const uint32_t wid = blockIdx.x * 4u + wave;
+        g = wid / a.wpg8;
+        part = wid - (uint32_t)g * a.wpg8;
+    }
+    if (g >= a.groups) return;
+    uint32_t mk = 0;
+    if (lane < K) mk = dmarks[g * K + lane];
+    else if (lane < N) mk = pmarks[g * M + (lane - K)];
+    const uint64_t mask = __ballot(mk != 0) & ((1ull << N) - 1ull);
+    const int t = __builtin_popcountll(mask);
+    if (t == 0) return;
+    if (t > M) {
+        if (part == 0 && lane == 0 && a.failed) atomicAdd(a.failed, 1u);
+        return;
+    }
+    const int rec = ((const __attribute__((address_space(4))) int32_t*)lut)[mask];
+    if (rec < 0) {  // a singular decode matrix (explicit rows only): counted like t > m
+        if (part == 0 && lane == 0 && a.failed) atomicAdd(a.failed, 1u);
+        return;
+    }
+    const RTab R{records + rec, a.coff, a.t256};
+    const uint64_t pitch = a.pitch;
+    uint8_t* data_g = data + g * a.dgs;
+    uint8_t* par_g = parity + g * a.pgs;
+    // the k lowest unmarked ids, known from the mask alone: the loads issue before the record arrives
+    uint64_t avail = ~mask & ((1ull << N) - 1ull);
+    const uint8_t* src[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        const uint32_t s = (uint32_t)__builtin_ctzll(avail);
+        avail &= avail - 1;
+        src[c] = s < (uint32_t)K ? data_g + (uint64_t)s * pitch : par_g + (uint64_t)(s - K) * pitch;
+    }
+    const uint32_t col = part * 64u + lane;
+    if (col < a.cols8) repair_column_by_t<K, M, 2>(src, data_g, par_g, mask, R, t, pitch, (uint64_t)col * 8u);
+}
+
+// runtime k, t (every shape without an instance), and the byte path for layouts that are not
+// 16-B aligned.  One wave per group, column loop, output rows in chunks of RCH.
+template <bool VEC16>
+__global__ void __launch_bounds__(256) k_repair_any(RepairArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t g = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (g >= a.groups) return;
+    const int k = a.k, m = a.m, n = k + m;  // n <= QFEC_LUT_MAX_N
+    uint32_t mk = 0;
+    if (lane < k) mk = a.dmarks[g * (uint64_t)k + lane];
+    else if (lane < n) mk = a.pmarks[g * (uint64_t)m + (lane - k)];
+    const uint32_t mask = (uint32_t)(__ballot(mk != 0) & ((1ull << n) - 1ull));
+    if (!mask) return;
+    const int rec = __builtin_amdgcn_readfirstlane(a.lut[mask]);
+    if (rec < 0) {
+        if (rec == QFEC_REC_FAIL && lane == 0 && a.failed) atomicAdd(a.failed, 1u);
+        return;
+    }
+    const uint32_t* __restrict__ r = a.records + rec;
+    const int t = (int)r[0];
+    const uint32_t quirk = r[1];
+    const uint32_t* surv = r + a.surv_off;
+    const uint32_t* lost = r + a.lost_off;
+    const uint32_t* offs = r + a.coff;
+    uint8_t* data_g = a.data + g * a.dgs;
+    uint8_t* par_g = a.parity + g * a.pgs;
+    auto row = [&](uint32_t s) -> uint8_t* {
+        return s < (uint32_t)k ? data_g + (uint64_t)s * a.pitch : par_g + (uint64_t)(s - k) * a.pitch;
+    };
+
+    for (uint32_t col = lane; col < a.cols; col += 64) {
+        for (int j0 = 0; j0 < t; j0 += RCH) {
+            if (VEC16) {
+                const uint64_t off = (uint64_t)col * 16u;
+                uint4 acc[RCH];
+#pragma unroll
+                for (int j = 0; j < RCH; ++j) {
+                    acc[j] = make_uint4(0, 0, 0, 0);
+                    const int jj = j0 + j;
+                    if (jj < t && ((quirk >> jj) & 1u)) acc[j] = *reinterpret_cast<const uint4*>(row(lost[jj]) + off);
+                }
+                for (int c = 0; c < k; ++c) {
+                    const uint4 v = ld16(row(surv[c]) + off);
+                    Sel s[4];
+                    sel16(s, v);
+#pragma unroll
+                    for (int j = 0; j < RCH; ++j)
+                        if (j0 + j < t) gf_mac16(acc[j], s, a.t256 + (offs[(j0 + j) * k + c] >> 2));
+                }
+#pragma unroll
+                for (int j = 0; j < RCH; ++j)
+                    if (j0 + j < t) st16(row(lost[j0 + j]) + off, acc[j]);
+            } else {
+                const uint64_t off = col;
+                uint32_t acc[RCH];
+#pragma unroll
+                for (int j = 0; j < RCH; ++j) {
+                    acc[j] = 0;
+                    const int jj = j0 + j;
+                    if (jj < t && ((quirk >> jj) & 1u)) acc[j] = row(lost[jj])[off];
+                }
+                for (int c = 0; c < k; ++c) {
+                    const Sel s = gf_sel((uint32_t)row(surv[c])[off]);
+#pragma unroll
+                    for (int j = 0; j < RCH; ++j)
+                        if (j0 + j < t) {
+                            const uint32_t* tc = a.t256 + (offs[(j0 + j) * k + c] >> 2);
+                            acc[j] ^= gf_mul4(s, tc[0], tc[1], tc[2], tc[3], tc[4]);
+                        }
+                }
+#pragma unroll
+                for (int j = 0; j < RCH; ++j)
+                    if (j0 + j < t) row(lost[j0 + j])[off] = (uint8_t)acc[j];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ utilities
 
 __global__ void __launch_bounds__(256) k_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed) {
@@ -811,6 +992,44 @@ hipError_t launch_reconstruct(const ReconArgs& a, hipStream_t stream) {
     QFEC_REC_CASE(8, 2)
     QFEC_REC_CASE(20, 4)
     hipLaunchKernelGGL((k_reconstruct_any<true>), dim3(grid), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// the reconstruct's auto body for every instance: 8-B lanes, one group per block where a group is
+// at most 4 waves (rows up to 2 KiB), else 4-wave blocks over (group, slab)
+#define QFEC_REP_CASE(KK, MM)                                                                                   \
+    if (a.k == KK && a.m == MM) {                                                                               \
+        if (a.wpg8 >= 1 && a.wpg8 <= 4)                                                                         \
+            hipLaunchKernelGGL((k_repair_perm<KK, MM, true>), dim3((unsigned)a.groups), dim3(64u * a.wpg8), 0, \
+                               stream, a, a.data, a.parity, a.dmarks, a.pmarks, a.lut, a.records);              \
+        else                                                                                                    \
+            hipLaunchKernelGGL((k_repair_perm<KK, MM, false>), dim3(grid_for(a.groups * (uint64_t)a.wpg8, 4)), \
+                               dim3(256), 0, stream, a, a.data, a.parity, a.dmarks, a.pmarks, a.lut, a.records); \
+        return hipGetLastError();                                                                               \
+    }
+
+hipError_t launch_repair(const RepairArgs& a, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    if (a.k + a.m > QFEC_LUT_MAX_N) return hipErrorInvalidValue;
+    if (a.groups * (uint64_t)std::max(a.wpg8, 1u) > 0x7FFFFFFFull) return hipErrorInvalidValue;  // caller chunks
+    const unsigned grid = grid_for(a.groups, 4);
+    if (!a.vec16) {
+        hipLaunchKernelGGL((k_repair_any<false>), dim3(grid), dim3(256), 0, stream, a);
+        return hipGetLastError();
+    }
+    QFEC_REP_CASE(10, 3)
+    QFEC_REP_CASE(16, 4)
+    QFEC_REP_CASE(4, 2)
+    QFEC_REP_CASE(2, 1)
+    QFEC_REP_CASE(3, 2)
+    QFEC_REP_CASE(8, 4)
+    QFEC_REP_CASE(12, 4)
+    QFEC_REP_CASE(5, 3)
+    QFEC_REP_CASE(6, 2)
+    QFEC_REP_CASE(7, 1)
+    QFEC_REP_CASE(8, 2)
+    QFEC_REP_CASE(20, 4)
+    hipLaunchKernelGGL((k_repair_any<true>), dim3(grid), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

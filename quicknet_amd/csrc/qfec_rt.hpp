@@ -7,6 +7,7 @@
 //                      classification of caller shard pointers
 //   qfec_pipe.cpp      qfec_pipe_* (host batches streamed over several streams and devices)
 //   qfec_wire_api.cpp  the datagram / framing entry points (qfec_pack_*, qfec_unpack_*, ...)
+//   qfec_repair.cpp    qfec_repair (its LUT and records) and qfec_verify
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -149,6 +150,9 @@ struct DevTables {
     int32_t* d_lut = nullptr;    // [2^n]
     uint32_t* d_rec = nullptr;   // decode records
     uint64_t rec_version = ~0ull;
+    int32_t* d_rep_lut = nullptr;   // [2^n] repair: full n-bit mask -> compact record (qfec_repair.cpp)
+    uint32_t* d_rep_rec = nullptr;  // compact repair records
+    uint64_t rep_version = ~0ull;
 };
 
 struct qfec_code {

@@ -298,6 +298,8 @@ void free_code(qfec_code* c) {
         if (kv.second.d_enc) (void)hipFree(kv.second.d_enc);
         if (kv.second.d_lut) (void)hipFree(kv.second.d_lut);
         if (kv.second.d_rec) (void)hipFree(kv.second.d_rec);
+        if (kv.second.d_rep_lut) (void)hipFree(kv.second.d_rep_lut);
+        if (kv.second.d_rep_rec) (void)hipFree(kv.second.d_rep_rec);
     }
     if (have) (void)hipSetDevice(prev);
     delete c;
