@@ -169,6 +169,56 @@ int qfec_verify(qfec_code *code, const unsigned char *d_data, const unsigned cha
                 unsigned int *d_bad_rows /* [groups], nullable */,
                 unsigned int *d_bad_groups /* counter, accumulates, nullable */, void *stream);
 
+/* Which shard is wrong?  qfec_verify says whether a group's parity matches its data; qfec_locate
+ * names the ONE shard, data or parity, whose corruption explains the mismatch, so that it can be
+ * marked for qfec_repair.  A code with m >= 2 parity rows has minimum distance m + 1 >= 3 and can
+ * locate (and so correct) one corrupted shard per group.  Per byte position the syndromes are
+ * s_j = parity_j ^ sum_i rows[j][i] x data_i; an error in data shard i gives
+ * s_j = (rows[j][i] / rows[0][i]) x s_0 for every j, an error in parity row j0 gives s_j0 != 0 and
+ * every other s_j = 0.  A shard is a candidate only if its relation holds in EVERY byte of
+ * [0, block_size).  d_culprit[g] is written for every group:
+ *   0 .. k+m-1          the one candidate (data shards 0..k-1, parity rows k..k+m-1)
+ *   QFEC_LOC_CLEAN      every syndrome is zero: parity matches data
+ *   QFEC_LOC_MULTI      inconsistent, and no single shard explains it (two or more corrupted shards)
+ *   QFEC_LOC_AMBIGUOUS  more than one single shard explains it; only codes from explicit rows that
+ *                       are not MDS (two proportional columns of [rows | I]) can give this
+ * With m >= 3 (distance >= 4) two corrupted shards never pass for one.  With m = 2 they can: the
+ * verdict for more than one corrupted shard is then undefined (a wrong id is possible), which is
+ * inherent to a distance-3 code.
+ * d_marks (rs.c layout, groups * (k + m) bytes, may be NULL) is written for every group: 1 at the
+ * culprit, 0 everywhere else (all zero for CLEAN, MULTI and AMBIGUOUS groups), ready for
+ * qfec_repair.  d_counts ([3], may be NULL; accumulated, not reset) gains 1 per located, MULTI and
+ * AMBIGUOUS group.  Layouts, pitch, stream and the meaning of [block_size, pitch) are qfec_verify's:
+ * bytes past block_size of either buffer never influence a result, and nothing in d_data / d_parity
+ * is written.  Asynchronous on `stream`, no host synchronisation and no read-back; the per-group
+ * working words come from stream-ordered scratch.  A consistent batch costs what qfec_verify costs
+ * (reads (k + m) rows per group).  QFEC_EUNSUP, decided on the host before a device is touched:
+ * m < 2; k > 32 or m > 32; any zero coefficient in the parity rows. */
+#define QFEC_LOC_CLEAN     (-1)  /* parity matches data */
+#define QFEC_LOC_MULTI     (-2)  /* inconsistent, and no single shard explains it */
+#define QFEC_LOC_AMBIGUOUS (-3)  /* more than one single shard explains it (non-MDS explicit rows only) */
+int qfec_locate(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                long long groups, int block_size, long long pitch,
+                int *d_culprit            /* [groups]: shard id 0..k+m-1, or QFEC_LOC_* */,
+                unsigned char *d_marks    /* rs.c layout, groups*(k+m) bytes, nullable */,
+                unsigned int *d_counts    /* [3] located, multi, ambiguous; accumulates; nullable */,
+                void *stream);
+
+/* qfec_locate into stream-ordered scratch marks, then qfec_repair with those marks, in one call: a
+ * group with one corrupted shard is back to its original bytes in [0, block_size); CLEAN groups and
+ * MULTI / AMBIGUOUS groups are untouched byte for byte (the latter are reported only, in d_culprit
+ * ([groups], may be NULL) and d_counts ([3], may be NULL; accumulated)).  Asynchronous on `stream`
+ * once the repair LUT exists (qfec_prepare_repair, or the first call).  QFEC_EUNSUP as for
+ * qfec_locate, and for k + m > 24 (qfec_repair's limit), checked before anything is launched. */
+int qfec_scrub(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+               long long groups, int block_size, long long pitch,
+               int *d_culprit /* nullable */, unsigned int *d_counts /* [3], nullable */, void *stream);
+
+/* The host-built constants of qfec_locate: r_{j,i} = rows[j][i] / rows[0][i] at
+ * out[i*(m-1) + (j-1)], j = 1..m-1.  QFEC_EUNSUP as for qfec_locate.  CPU only, like
+ * qfec_repair_rows. */
+int qfec_locate_ratios(const qfec_code *code, unsigned char *out /* k*(m-1): r_{j,i} at [i*(m-1)+(j-1)] */);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

@@ -18,6 +18,7 @@ EXPORTS = {
     "qfec.h": ["qfec_code_new", "qfec_code_from_rows", "qfec_code_free", "qfec_code_rows", "qfec_code_shape",
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
+               "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
                "qfec_pipe_new", "qfec_pipe_free", "qfec_pipe_encode", "qfec_pipe_reconstruct", "qfec_pipe_wait", "qfec_pipe_slots",
                "qfec_fec_code", "qfec_rs_code", "qfec_fec_matrix", "qfec_pack_datagrams", "qfec_unpack_datagrams",
                "qfec_frame_udp", "qfec_unframe_udp", "qfec_pack_frames", "qfec_unpack_frames", "qfec_gather_rows", "qfec_synth_fill", "qfec_probe_stream", "qfec_probe_reconstruct", "qfec_rs_host_devices", "qfec_rs_host_devices_get",
@@ -34,6 +35,7 @@ QFEC_CAUCHY = 0
 QFEC_VANDERMONDE = 1
 QFEC_VARIANT_PERM = 0
 QFEC_VARIANT_LDSLOG = 1
+QFEC_LOC_CLEAN, QFEC_LOC_MULTI, QFEC_LOC_AMBIGUOUS = -1, -2, -3  # qfec_locate verdicts (include/qfec.h)
 
 _lib = None
 
@@ -76,6 +78,9 @@ def lib():
         "qfec_prepare_repair": (i, [vp]),
         "qfec_repair_rows": (i, [vp, vp, vp, vp, vp]),
         "qfec_verify": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
+        "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
+        "qfec_locate_ratios": (i, [vp, vp]),
         "qfec_pipe_new": (vp, [vp, i, i, ll]),
         "qfec_pipe_free": (None, [vp]),
         "qfec_pipe_encode": (i, [vp, vp, vp, vp, ll, i, ll]),

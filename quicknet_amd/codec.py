@@ -320,6 +320,58 @@ class Code:
                                 _stream_handle(stream)), "qfec_verify")
         return bad_rows
 
+    def locate(self, data, parity, block_size=None, culprit=None, marks=None, counts=None, stream=None):
+        """Which single shard of each group is corrupted (qfec_locate)?  Returns culprit, a device
+        int32 [G] tensor (allocated when not given): the shard id 0..k+m-1, or QFEC_LOC_CLEAN (-1),
+        QFEC_LOC_MULTI (-2), QFEC_LOC_AMBIGUOUS (-3).  marks: optional device uint8 [G*k + G*m]
+        (rs.c layout), written for every group: 1 at the culprit, else 0 -- ready for repair().
+        counts: optional device int32/uint32 [3] located / multi / ambiguous (accumulates)."""
+        import torch
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
+        if culprit is None:
+            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
+        elif culprit.numel() != G:
+            raise QfecError(f"locate: culprit has {culprit.numel()} elements for {G} groups")
+        if marks is not None and marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"locate: marks has {marks.numel()} elements for {G} groups of {self.k + self.m}")
+        if counts is not None and counts.numel() != 3:
+            raise QfecError(f"locate: counts has {counts.numel()} elements, not 3")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_locate(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
+                                pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks, what="marks"),
+                                _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate")
+        return culprit
+
+    def scrub(self, data, parity, block_size=None, culprit=None, counts=None, stream=None):
+        """locate() + repair() of the located shard in one call (qfec_scrub): a group with one
+        corrupted shard is rewritten to its original bytes, MULTI / AMBIGUOUS groups are left as
+        they are and only reported.  Returns culprit as locate() does."""
+        import torch
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
+        if culprit is None:
+            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
+        elif culprit.numel() != G:
+            raise QfecError(f"scrub: culprit has {culprit.numel()} elements for {G} groups")
+        if counts is not None and counts.numel() != 3:
+            raise QfecError(f"scrub: counts has {counts.numel()} elements, not 3")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_scrub(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
+                               pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                               _stream_handle(stream)), "qfec_scrub")
+        return culprit
+
+    def locate_ratios(self):
+        """The constants of locate(): uint8 [k, m-1], r[i, j-1] = rows[j, i] / rows[0, i] (CPU only)."""
+        out = np.zeros((self.k, max(self.m - 1, 0)), dtype=np.uint8)
+        scratch = np.zeros(max(out.size, 1), dtype=np.uint8)
+        check(lib().qfec_locate_ratios(self._h, scratch.ctypes.data), "qfec_locate_ratios")
+        out[:] = scratch[:out.size].reshape(out.shape)
+        return out
+
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15
     def pack_datagrams(self, payload, offsets, sizes, seq, checksum=True, shard_pitch=None, wire_pitch=None,
                        stream=None):

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "qfec_internal.hpp"
 
 namespace qfec {
@@ -100,6 +102,24 @@ __device__ __forceinline__ void st16(uint8_t* p, const uint4& v) {
 __device__ __forceinline__ uint64_t fast_div(uint64_t n, const DivMagic& d) {
     // n < 2^32 and d.mul < 2^33 (see make_div_magic); exact.
     return d.pow2 ? (n >> d.shift) : ((n * d.mul) >> (32 + d.shift));
+}
+
+// ------------------------------------------------------------------ compares under block_size
+// (qfec_verify.hip, qfec_locate.hip: only bytes [0, block_size) of a row count)
+
+// mask of the first `vb` bytes of a dword (vb <= 0: none, vb >= 4: all)
+__device__ __forceinline__ uint32_t head_bytes(int vb) {
+    return vb >= 4 ? 0xFFFFFFFFu : vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u);
+}
+
+// bytes of the 16-B column `col` that lie inside the row's block_size bytes, as four dword masks
+__device__ __forceinline__ uint4 column_mask(uint32_t block, uint32_t col) {
+    const int nb = (int)std::min<uint32_t>(16u, block - col * 16u);
+    return make_uint4(head_bytes(nb), head_bytes(nb - 4), head_bytes(nb - 8), head_bytes(nb - 12));
+}
+
+__device__ __forceinline__ bool differs(const uint4& acc, const uint4& p, const uint4& mk) {
+    return (((acc.x ^ p.x) & mk.x) | ((acc.y ^ p.y) & mk.y) | ((acc.z ^ p.z) & mk.z) | ((acc.w ^ p.w) & mk.w)) != 0;
 }
 
 }  // namespace qfec

@@ -112,6 +112,37 @@ struct VerifyArgs {
     int vec16;
 };
 
+// single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
+// syndrome tests every data shard as the culprit
+struct LocateArgs {
+    const uint8_t* data;      // [groups][k][pitch]
+    const uint8_t* parity;    // [groups][m][pitch]
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    const uint32_t* rtab;     // [k][m-1][QFEC_TAB_STRIDE] perm tables of r_{j,i} = P[j][i] / P[0][i], j = 1..m-1
+    unsigned int* bad_rows;   // [groups] of this launch, zeroed before it; bit j = syndrome j is non-zero
+    unsigned int* cand;       // [groups] of this launch, all ones before it; bit i = data shard i explains
+                              // every non-zero syndrome column seen so far
+    uint64_t work;            // groups * cols lanes (< 2^31)
+    uint64_t pitch;
+    uint64_t dgs, pgs;
+    DivMagic cols_div;
+    uint32_t cols;            // 16-B columns (vec16) or bytes per row
+    uint32_t block;           // block_size: bytes of a row that count
+    int k, m;                 // 2 <= m <= 32, k <= 32
+    int vec16;
+};
+
+// the verdict per group from its two words, after the last launch_locate of a call
+struct LocateFinishArgs {
+    const unsigned int* bad_rows;  // [groups]
+    const unsigned int* cand;      // [groups]
+    int* culprit;                  // [groups] shard id or QFEC_LOC_*
+    uint8_t* marks;                // rs.c layout, groups * (k + m) bytes; may be NULL
+    unsigned int* counts;          // [3] located, multi, ambiguous; may be NULL
+    uint64_t groups;
+    int k, m;
+};
+
 // FEC datagram batches (qfec_wire.hip): shards[G][n][pitch], wire[G][n][wire_pitch]
 struct WireArgs {
     const uint8_t* payload;   // send: concatenated payloads (16 readable bytes past the last)
@@ -201,6 +232,8 @@ hipError_t launch_encode(const EncodeArgs& a, int variant, hipStream_t stream);
 hipError_t launch_reconstruct(const ReconArgs& a, hipStream_t stream);
 hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
 hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
+hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
+hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);

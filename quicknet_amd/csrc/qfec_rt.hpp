@@ -8,6 +8,7 @@
 //   qfec_pipe.cpp      qfec_pipe_* (host batches streamed over several streams and devices)
 //   qfec_wire_api.cpp  the datagram / framing entry points (qfec_pack_*, qfec_unpack_*, ...)
 //   qfec_repair.cpp    qfec_repair (its LUT and records) and qfec_verify
+//   qfec_locate.cpp    qfec_locate (its ratio tables), qfec_scrub
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -153,6 +154,8 @@ struct DevTables {
     int32_t* d_rep_lut = nullptr;   // [2^n] repair: full n-bit mask -> compact record (qfec_repair.cpp)
     uint32_t* d_rep_rec = nullptr;  // compact repair records
     uint64_t rep_version = ~0ull;
+    uint32_t* d_loc = nullptr;      // [k][m-1][8] locate: perm tables of P[j][i] / P[0][i] (qfec_locate.cpp)
+    uint64_t loc_version = ~0ull;
 };
 
 struct qfec_code {

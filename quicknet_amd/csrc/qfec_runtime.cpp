@@ -300,6 +300,7 @@ void free_code(qfec_code* c) {
         if (kv.second.d_rec) (void)hipFree(kv.second.d_rec);
         if (kv.second.d_rep_lut) (void)hipFree(kv.second.d_rep_lut);
         if (kv.second.d_rep_rec) (void)hipFree(kv.second.d_rep_rec);
+        if (kv.second.d_loc) (void)hipFree(kv.second.d_loc);
     }
     if (have) (void)hipSetDevice(prev);
     delete c;

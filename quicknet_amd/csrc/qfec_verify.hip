@@ -22,20 +22,8 @@
 
 namespace qfec {
 
-// mask of the first `vb` bytes of a dword (vb <= 0: none, vb >= 4: all)
-__device__ __forceinline__ uint32_t head_bytes(int vb) {
-    return vb >= 4 ? 0xFFFFFFFFu : vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u);
-}
-
-// bytes of the 16-B column `col` that lie inside the row's block_size bytes, as four dword masks
-__device__ __forceinline__ uint4 column_mask(uint32_t block, uint32_t col) {
-    const int nb = (int)std::min<uint32_t>(16u, block - col * 16u);
-    return make_uint4(head_bytes(nb), head_bytes(nb - 4), head_bytes(nb - 8), head_bytes(nb - 12));
-}
-
-__device__ __forceinline__ bool differs(const uint4& acc, const uint4& p, const uint4& mk) {
-    return (((acc.x ^ p.x) & mk.x) | ((acc.y ^ p.y) & mk.y) | ((acc.z ^ p.z) & mk.z) | ((acc.w ^ p.w) & mk.w)) != 0;
-}
+// head_bytes, column_mask and differs (the tail-byte mask and the compare under it) are in
+// qfec_device.hpp, shared with qfec_locate.hip.
 
 // bad = this lane's row bits for group g (0 for idle lanes).  Every lane of the wave calls it.
 __device__ __forceinline__ void verify_report(const VerifyArgs& a, uint32_t g, uint32_t bad) {
