@@ -219,6 +219,83 @@ int qfec_scrub(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
  * qfec_repair_rows. */
 int qfec_locate_ratios(const qfec_code *code, unsigned char *out /* k*(m-1): r_{j,i} at [i*(m-1)+(j-1)] */);
 
+/* Which SURVIVING shard is wrong, in a group that also has lost shards?  qfec_locate needs all k + m
+ * shards of a group; on a lossy link that is the rare case.  A group with t <= m - 2 marked (lost)
+ * shards still holds m - t >= 2 shards more than the k a decode needs, and those can name one
+ * corrupted survivor exactly as the m parity rows do for a complete group.  All arithmetic is true
+ * GF(2^8) products from the code's parity rows, as in qfec_verify and qfec_locate (no rs.c stale-row
+ * quirk).  Per group, with E the marked shards and t = |E|:
+ *   K    the k lowest unmarked shard ids: the survivors qfec_repair decodes from
+ *   R    the other m - t unmarked ids, the spares; always parity rows (K holds every unmarked data shard)
+ *   A_x  for each spare x, the row over K that qfec_repair_rows returns for x under the mask E + R
+ *        (m bits set, K unchanged); s_x = shard_x ^ sum_{i in K} A_x[i] x shard_i is its syndrome
+ * [A | I] over (K, R) is the parity check of the code punctured at E, an MDS [n - t, k] code of
+ * distance m - t + 1.  An error in spare x0 alone gives s_x0 != 0 and every other s_x = 0; an error
+ * in the shard at position i of K alone gives s_x = (A_x[i] / A_x0[i]) x s_x0 for the first spare x0
+ * and every other x.  A shard is a candidate only if its relation holds in EVERY byte of
+ * [0, block_size).  Marked shards are never read and never candidates.  d_culprit[g]:
+ *   t > m                        QFEC_LOC_LOST: under-determined
+ *   t = m                        QFEC_LOC_UNCHECKED: no spare, nothing can be checked
+ *   t < m, all syndromes zero    QFEC_LOC_CLEAN
+ *   t < m, one candidate         its shard id 0..k+m-1
+ *   t < m, no candidate          QFEC_LOC_MULTI
+ *   t < m, several candidates    QFEC_LOC_AMBIGUOUS
+ * With ONE spare (t = m - 1) there is no ratio to test: an inconsistent group is then AMBIGUOUS,
+ * because every shard of K and the spare itself explain it equally well.  That is the honest answer
+ * of a distance-2 code: it detects, it cannot locate.
+ * With t = 0 the definitions reduce to qfec_locate's (K is the data, R the parity, A the parity
+ * rows), and the verdicts are identical to qfec_locate's.  With m - t >= 3 spares two corrupted
+ * survivors are never taken for one; with exactly 2 spares the verdict for two corrupted survivors is
+ * undefined (a wrong id is possible), as for m = 2 in qfec_locate.
+ * d_marks is in the rs.c layout, as for qfec_repair (non-zero = lost).  d_marks_out (same layout, may
+ * be NULL, may be d_marks itself) is written for every group: the input marks as 0 / 1, plus 1 at the
+ * culprit when one is located -- ready for qfec_repair, since a culprit exists only when t + 1 <= m - 1.
+ * d_counts ([5], may be NULL; accumulated, not reset) gains 1 per located, MULTI, AMBIGUOUS,
+ * UNCHECKED and LOST group.  Layouts, pitch and the meaning of [block_size, pitch) are qfec_locate's;
+ * nothing in d_data / d_parity is written.  Asynchronous on `stream` once the pattern tables exist
+ * (one record per mask with t <= m - 1 and a 2^(k+m)-entry LUT, built by qfec_prepare_locate_erased
+ * or on the first call); the per-group working words come from stream-ordered scratch.  Reads the
+ * k + m - t unmarked rows of a group.  On complete groups qfec_locate is the faster call (16-B lanes).
+ * QFEC_EUNSUP, decided on the host before anything is launched: everything qfec_locate refuses
+ * (m < 2; k or m > 32; a zero coefficient in the parity rows); k + m > 24 (the LUT is keyed by the
+ * whole mask, as qfec_repair's); a code from explicit rows where some mask with t <= m - 2 has a zero
+ * in A, or some mask with t <= m - 1 a singular matrix over K: the punctured code is then not MDS.
+ * Codes from qfec_code_new never hit the last case.  Also refused: a shape whose records (one per mask
+ * with t <= m - 1) would take more than 256 MiB, which needs m >= 8 at k + m near 24. */
+#define QFEC_LOC_UNCHECKED (-4)  /* t = m: no spare row, nothing can be checked */
+#define QFEC_LOC_LOST      (-5)  /* t > m: under-determined */
+int qfec_locate_erased(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                       const unsigned char *d_marks      /* rs.c layout, as qfec_repair; non-zero = lost */,
+                       long long groups, int block_size, long long pitch,
+                       int *d_culprit                    /* [groups] */,
+                       unsigned char *d_marks_out        /* rs.c layout, nullable, may equal d_marks */,
+                       unsigned int *d_counts            /* [5] located, multi, ambiguous, unchecked, lost; accumulates; nullable */,
+                       void *stream);
+int qfec_prepare_locate_erased(qfec_code *code);
+
+/* qfec_locate_erased into stream-ordered scratch marks, then qfec_repair with them, in one call: the
+ * lost shards and the one corrupted survivor of a group are both rewritten to the original bytes in
+ * [0, block_size).  MULTI, AMBIGUOUS and LOST groups are untouched byte for byte (MULTI / AMBIGUOUS:
+ * their lost shards are NOT rebuilt, a rebuild would carry the corruption into them; they are reported
+ * in d_culprit ([groups], may be NULL) and d_counts ([5], may be NULL)).  UNCHECKED groups, and CLEAN
+ * groups that have lost shards, are repaired exactly as qfec_repair would repair them -- for UNCHECKED
+ * ones from survivors nothing could check.  *d_failed (may be NULL) is qfec_repair's counter: it gains
+ * 1 per LOST group.  QFEC_EUNSUP as for qfec_locate_erased, before anything is launched. */
+int qfec_scrub_erased(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                      const unsigned char *d_marks, long long groups, int block_size, long long pitch,
+                      int *d_culprit /* nullable */, unsigned int *d_counts /* [5], nullable */,
+                      unsigned int *d_failed /* qfec_repair's counter, nullable */, void *stream);
+
+/* The host-built constants of qfec_locate_erased for one group (group-order marks[n]): survivors_out
+ * (k) = K, spares_out (m - t) = R, rows_out ((m - t) x k) = A, ratios_out (nullable) = A_x[i] / A_x0[i]
+ * at [i*(m-t-1) + (x-1)], x = 1..m-t-1, x0 the first spare.  Returns the number of spares m - t, 0 when
+ * t = m (only survivors_out is written), -1 when t > m; QFEC_EUNSUP when the matrix over K is singular.
+ * Any k + m.  CPU only, like qfec_repair_rows. */
+int qfec_locate_erased_plan(const qfec_code *code, const unsigned char *marks_n,
+                            int *survivors_out /* k */, int *spares_out /* m - t */,
+                            unsigned char *rows_out /* (m-t)*k: A */,
+                            unsigned char *ratios_out /* k*(m-t-1): A_x[i]/A_x0[i] at [i*(m-t-1)+(x-1)], nullable */);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

@@ -19,6 +19,7 @@ EXPORTS = {
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
+               "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
                "qfec_pipe_new", "qfec_pipe_free", "qfec_pipe_encode", "qfec_pipe_reconstruct", "qfec_pipe_wait", "qfec_pipe_slots",
                "qfec_fec_code", "qfec_rs_code", "qfec_fec_matrix", "qfec_pack_datagrams", "qfec_unpack_datagrams",
                "qfec_frame_udp", "qfec_unframe_udp", "qfec_pack_frames", "qfec_unpack_frames", "qfec_gather_rows", "qfec_synth_fill", "qfec_probe_stream", "qfec_probe_reconstruct", "qfec_rs_host_devices", "qfec_rs_host_devices_get",
@@ -36,6 +37,7 @@ QFEC_VANDERMONDE = 1
 QFEC_VARIANT_PERM = 0
 QFEC_VARIANT_LDSLOG = 1
 QFEC_LOC_CLEAN, QFEC_LOC_MULTI, QFEC_LOC_AMBIGUOUS = -1, -2, -3  # qfec_locate verdicts (include/qfec.h)
+QFEC_LOC_UNCHECKED, QFEC_LOC_LOST = -4, -5  # qfec_locate_erased: no spare row to check with; under-determined
 
 _lib = None
 
@@ -81,6 +83,10 @@ def lib():
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),
+        "qfec_locate_erased": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_prepare_locate_erased": (i, [vp]),
+        "qfec_scrub_erased": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_locate_erased_plan": (i, [vp, vp, vp, vp, vp, vp]),
         "qfec_pipe_new": (vp, [vp, i, i, ll]),
         "qfec_pipe_free": (None, [vp]),
         "qfec_pipe_encode": (i, [vp, vp, vp, vp, ll, i, ll]),

@@ -372,6 +372,80 @@ class Code:
         out[:] = scratch[:out.size].reshape(out.shape)
         return out
 
+    def prepare_locate_erased(self):
+        check(lib().qfec_prepare_locate_erased(self._h), "qfec_prepare_locate_erased")
+
+    def _erased_args(self, what, data, parity, marks, culprit, counts):
+        import torch
+        G, k, pitch = data.shape
+        n = self.k + self.m
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch) or marks.numel() != G * n:
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
+                            f"marks {marks.numel()} for ({self.k},{self.m})")
+        if culprit is None:
+            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
+        elif culprit.numel() != G:
+            raise QfecError(f"{what}: culprit has {culprit.numel()} elements for {G} groups")
+        if counts is not None and counts.numel() != 5:
+            raise QfecError(f"{what}: counts has {counts.numel()} elements, not 5")
+        return G, pitch, culprit
+
+    def locate_erased(self, data, parity, marks, block_size=None, culprit=None, marks_out=None, counts=None,
+                      stream=None):
+        """Which single surviving shard of each group is corrupted, when groups also have lost shards
+        (qfec_locate_erased)?  marks: device uint8 [G*k + G*m] (rs.c layout, non-zero = lost).
+        Returns culprit, a device int32 [G] tensor (allocated when not given): the shard id, or
+        QFEC_LOC_CLEAN (-1), MULTI (-2), AMBIGUOUS (-3), UNCHECKED (-4: t = m), LOST (-5: t > m).
+        marks_out: optional device uint8 like marks (may be marks itself), written for every group:
+        the marks as 0 / 1 plus 1 at a located culprit -- ready for repair().  counts: optional device
+        int32/uint32 [5] located / multi / ambiguous / unchecked / lost (accumulates)."""
+        G, pitch, culprit = self._erased_args("locate_erased", data, parity, marks, culprit, counts)
+        if marks_out is not None and marks_out.numel() != marks.numel():
+            raise QfecError(f"locate_erased: marks_out has {marks_out.numel()} elements, marks {marks.numel()}")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_locate_erased(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                       _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                       _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks_out, what="marks_out"),
+                                       _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate_erased")
+        return culprit
+
+    def scrub_erased(self, data, parity, marks, block_size=None, culprit=None, counts=None, failed=None, stream=None):
+        """locate_erased() + repair() in one call (qfec_scrub_erased): lost shards and the one
+        corrupted survivor of a group are rewritten to their original bytes; MULTI, AMBIGUOUS and
+        LOST groups are left as they are and only reported; UNCHECKED groups and CLEAN groups with
+        lost shards are repaired as repair() would.  failed: optional device int32/uint32 [1],
+        repair()'s counter (the LOST groups).  Returns culprit as locate_erased() does."""
+        G, pitch, culprit = self._erased_args("scrub_erased", data, parity, marks, culprit, counts)
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_scrub_erased(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                      _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                      _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                                      _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_scrub_erased")
+        return culprit
+
+    def locate_erased_plan(self, marks_n):
+        """The host constants of locate_erased() for one group-order mark vector over all n shards:
+        (spares, survivors[k], spare_ids[spares], rows[spares, k], ratios[k, spares-1]); spares = 0
+        when t = m (survivors only, the rest None), -1 when t > m (all None).  CPU only."""
+        marks_n = np.ascontiguousarray(marks_n, dtype=np.uint8)
+        if marks_n.size != self.k + self.m:
+            raise QfecError(f"locate_erased_plan: {marks_n.size} marks for ({self.k},{self.m})")
+        m1 = max(self.m, 1)
+        surv = np.zeros(self.k, dtype=np.int32)
+        spares = np.zeros(m1, dtype=np.int32)
+        rows = np.zeros(m1 * self.k, dtype=np.uint8)
+        ratios = np.zeros(m1 * self.k, dtype=np.uint8)
+        s = lib().qfec_locate_erased_plan(self._h, marks_n.ctypes.data, surv.ctypes.data, spares.ctypes.data,
+                                          rows.ctypes.data, ratios.ctypes.data)
+        if s < -1:
+            check(s, "qfec_locate_erased_plan")
+        if s < 0:
+            return s, None, None, None, None
+        if s == 0:
+            return 0, surv, None, None, None
+        return (s, surv, spares[:s].copy(), rows[:s * self.k].reshape(s, self.k).copy(),
+                ratios[:self.k * (s - 1)].reshape(self.k, s - 1).copy())
+
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15
     def pack_datagrams(self, payload, offsets, sizes, seq, checksum=True, shard_pitch=None, wire_pitch=None,
                        stream=None):

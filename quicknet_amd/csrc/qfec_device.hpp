@@ -99,13 +99,87 @@ __device__ __forceinline__ void st16(uint8_t* p, const uint4& v) {
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
 }
 
+// D dwords per lane, streamed (the reconstruct / repair / locate-erased bodies: 16-, 12- or 8-B columns)
+template <int D>
+__device__ __forceinline__ void ldv(uint32_t (&v)[D], const uint8_t* p) {
+    if constexpr (D == 4) {
+        const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else if constexpr (D == 3) {  // merged into one global_load_dwordx3 ... nt
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        v[0] = __builtin_nontemporal_load(q);
+        v[1] = __builtin_nontemporal_load(q + 1);
+        v[2] = __builtin_nontemporal_load(q + 2);
+    } else {
+        static_assert(D == 2, "4, 3 or 2 dwords per lane");
+        const u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+        v[0] = t.x; v[1] = t.y;
+    }
+}
+
 __device__ __forceinline__ uint64_t fast_div(uint64_t n, const DivMagic& d) {
     // n < 2^32 and d.mul < 2^33 (see make_div_magic); exact.
     return d.pow2 ? (n >> d.shift) : ((n * d.mul) >> (32 + d.shift));
 }
 
+// ------------------------------------------------------------------ compact records
+// where a decode record's coefficient tables are: in the 256-entry table of every coefficient
+// value, at the byte offsets the record's header lists (RecordLayout::coff).  Reading only the
+// record's header keeps the records of all patterns cache-resident (RS(16,4): 4 844 records of
+// 2.4 KB would not fit the 4 MB L2; their headers do).  The tables are read through the
+// constant address space: loads from it are scalar (SMEM) whatever stores the kernel makes.
+typedef const __attribute__((address_space(4))) uint32_t* cptr32;
+typedef const __attribute__((address_space(4))) uint8_t* cptr8;
+struct RTab {
+    cptr32 rec;  // the record: [1] quirk flags, [coff + j*K + c] table byte offsets
+    cptr32 offs;
+    cptr32 t256;
+    __device__ RTab(const uint32_t* r, int coff, const uint32_t* t)
+        : rec((cptr32)r), offs((cptr32)r + coff), t256((cptr32)t) {}
+    __device__ __forceinline__ cptr32 at(int j, int c, int K) const {
+        return (cptr32)((cptr8)t256 + offs[j * K + c]);
+    }
+    __device__ __forceinline__ bool quirk(int j, int K) const { return (rec[1] >> j) & 1u; }
+    __device__ __forceinline__ void load5(int j, int c, int K, uint32_t (&t5)[5]) const {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) t5[i] = at(j, c, K)[i];
+    }
+};
+// acc[j] ^= sum_c coef(j, c) * x[c] over one column, exact E rows, survivors already in registers
+template <int K, int E, int D>
+__device__ __forceinline__ void recon_mac_core(const uint32_t (&x)[K][D], uint32_t (&acc)[E][D], const RTab& T) {
+#pragma unroll
+    for (int c = 0; c + 1 < K; c += 2) {
+        Sel sa[D], sb[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) { sa[d] = gf_sel(x[c][d]); sb[d] = gf_sel(x[c + 1][d]); }
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            uint32_t a5[5], b5[5];
+            T.load5(j, c, K, a5);
+            T.load5(j, c + 1, K, b5);
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc[j][d] = mac2(acc[j][d], sa[d], sb[d], a5, b5);
+        }
+    }
+    if (K & 1) {
+        Sel sl[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) sl[d] = gf_sel(x[K - 1][d]);
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            uint32_t t[5];
+            T.load5(j, K - 1, K, t);
+#pragma unroll
+            for (int d = 0; d < D; ++d)
+                acc[j][d] = xor3(acc[j][d], pp0(sl[d], t[0], t[1]), pp1(sl[d], t[2], t[3])) ^ pp2(sl[d], t[4]);
+        }
+    }
+}
+
+
 // ------------------------------------------------------------------ compares under block_size
-// (qfec_verify.hip, qfec_locate.hip: only bytes [0, block_size) of a row count)
+// (qfec_verify.hip, qfec_locate.hip, qfec_locate_erased.hip: only bytes [0, block_size) of a row count)
 
 // mask of the first `vb` bytes of a dword (vb <= 0: none, vb >= 4: all)
 __device__ __forceinline__ uint32_t head_bytes(int vb) {

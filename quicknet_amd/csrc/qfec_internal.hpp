@@ -18,6 +18,8 @@ constexpr int QFEC_TAB_STRIDE = 8;
 
 constexpr int QFEC_REC_NONE = -1;  // LUT: nothing erased in this group
 constexpr int QFEC_REC_FAIL = -2;  // LUT: more erased data than surviving parity
+constexpr int QFEC_LE_UNCHECKED = -1;  // locate-erased LUT: t = m, no spare row to check with
+constexpr int QFEC_LE_LOST = -2;       // locate-erased LUT: t > m
 constexpr int QFEC_LUT_MAX_N = 24; // n <= 24 -> 2^n-entry pattern LUT on the device
 
 constexpr int QFEC_VARIANT_PERM_I = 0;
@@ -143,6 +145,47 @@ struct LocateFinishArgs {
     int k, m;
 };
 
+// single-shard error location in groups that also have lost shards (qfec_locate_erased.hip): the
+// repair body's mapping (a wave sits inside one group); the syndromes are those of the m - t spare
+// parity rows over the k lowest unmarked shards
+struct LocErasedArgs {
+    const uint8_t* data;      // [groups][k][pitch]
+    const uint8_t* parity;    // [groups][m][pitch]
+    const uint8_t* dmarks;    // [groups][k] data marks of this launch's groups
+    const uint8_t* pmarks;    // [groups][m] parity marks of this launch's groups
+    const int32_t* lut;       // [2^n] full n-bit mask -> record offset (dwords) / QFEC_LE_*
+    const uint32_t* records;  // LocErasedLayout records (offsets into t256, no inline tables)
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    unsigned int* bad;        // [groups] of this launch, zeroed before it; bit x = syndrome of spare x is non-zero
+    unsigned int* cand;       // [groups] of this launch, all ones before it; bit c = the shard at position c of K
+                              // explains every non-zero syndrome column seen so far
+    uint64_t groups;
+    uint64_t pitch;
+    uint64_t dgs, pgs;        // bytes between groups: data rows, parity rows
+    uint32_t cols;            // 16-B columns (vec16) or bytes per row
+    uint32_t cols8, wpg8;     // 8-B columns per row and waves per group at 64 of them per wave
+    uint32_t block;           // block_size: bytes of a row that count
+    int k, m;                 // 2 <= m, k + m <= QFEC_LUT_MAX_N
+    int ids_off, aoff, roff;  // LocErasedLayout
+    int vec16;
+};
+
+// the verdict per group from its marks and its two words, after the last launch_locate_erased
+struct LocErasedFinishArgs {
+    const uint8_t* marks;          // rs.c layout over all groups (may be marks_out)
+    const int32_t* lut;
+    const uint32_t* records;
+    const unsigned int* bad;       // [groups]
+    const unsigned int* cand;      // [groups]
+    int* culprit;                  // [groups] shard id or QFEC_LOC_*; may be NULL
+    uint8_t* marks_out;            // rs.c layout; may be NULL, may be marks
+    unsigned int* counts;          // [5] located, multi, ambiguous, unchecked, lost; may be NULL
+    uint64_t groups;
+    int k, m;
+    int ids_off;
+    int scrub;                     // 1: MULTI / AMBIGUOUS groups get all-zero marks_out (qfec_repair leaves them alone)
+};
+
 // FEC datagram batches (qfec_wire.hip): shards[G][n][pitch], wire[G][n][wire_pitch]
 struct WireArgs {
     const uint8_t* payload;   // send: concatenated payloads (16 readable bytes past the last)
@@ -234,6 +277,8 @@ hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
 hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
+hipError_t launch_locate_erased(const LocErasedArgs& a, hipStream_t stream);
+hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);
@@ -298,5 +343,14 @@ void build_repair_record(const RecordLayout& L, int k, int t, int e, const uint8
                          const int* lost, bool rs_quirk, uint32_t* out);
 void build_record(const RecordLayout& L, int k, int e, const uint8_t* rows, const int* survivors,
                   const int* lost, bool rs_quirk, uint32_t* out);
+
+// Record of one erasure pattern for qfec_locate_erased (t <= m - 1 marked shards, S = m - t spares):
+// [0] S, [1] t, [ids_off + c] id of the shard at position c of K (the k lowest unmarked ids),
+// [ids_off + k + x] id of spare x (a parity row), [aoff + x*k + c] byte offset in the 256-entry
+// table of the perm table of A_x[c], [roff + c*(S-1) + (x-1)] the same for A_x[c] / A_0[c].
+struct LocErasedLayout {
+    int ids_off, aoff, roff, words;
+};
+LocErasedLayout loc_erased_layout(int k, int m);
 
 }  // namespace qfec

@@ -282,22 +282,6 @@ __device__ __forceinline__ int group_record(const ReconArgs& a, uint64_t g, int 
 // D = dwords per lane (4: 16-B columns, 2: 8-B columns for rows whose 16-B column count
 // leaves a wave mostly idle, e.g. B = 1400: 88 16-B columns on 2 waves, 175 8-B on 3).
 template <int D>
-__device__ __forceinline__ void ldv(uint32_t (&v)[D], const uint8_t* p) {
-    if constexpr (D == 4) {
-        const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else if constexpr (D == 3) {  // merged into one global_load_dwordx3 ... nt
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-        v[0] = __builtin_nontemporal_load(q);
-        v[1] = __builtin_nontemporal_load(q + 1);
-        v[2] = __builtin_nontemporal_load(q + 2);
-    } else {
-        static_assert(D == 2, "4, 3 or 2 dwords per lane");
-        const u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
-        v[0] = t.x; v[1] = t.y;
-    }
-}
-template <int D>
 __device__ __forceinline__ void stv(uint8_t* p, const uint32_t (&v)[D]) {
     if constexpr (D == 4) {
         const u32x4 t = {v[0], v[1], v[2], v[3]};
@@ -316,60 +300,6 @@ template <int D>
 __device__ __forceinline__ void ldv_plain(uint32_t (&v)[D], const uint8_t* p) {
 #pragma unroll
     for (int d = 0; d < D; ++d) v[d] = reinterpret_cast<const uint32_t*>(p)[d];
-}
-
-// where a decode record's coefficient tables are: in the 256-entry table of every coefficient
-// value, at the byte offsets the record's header lists (RecordLayout::coff).  Reading only the
-// record's header keeps the records of all patterns cache-resident (RS(16,4): 4 844 records of
-// 2.4 KB would not fit the 4 MB L2; their headers do).  The tables are read through the
-// constant address space: loads from it are scalar (SMEM) whatever stores the kernel makes.
-typedef const __attribute__((address_space(4))) uint32_t* cptr32;
-typedef const __attribute__((address_space(4))) uint8_t* cptr8;
-struct RTab {
-    cptr32 rec;  // the record: [1] quirk flags, [coff + j*K + c] table byte offsets
-    cptr32 offs;
-    cptr32 t256;
-    __device__ RTab(const uint32_t* r, int coff, const uint32_t* t)
-        : rec((cptr32)r), offs((cptr32)r + coff), t256((cptr32)t) {}
-    __device__ __forceinline__ cptr32 at(int j, int c, int K) const {
-        return (cptr32)((cptr8)t256 + offs[j * K + c]);
-    }
-    __device__ __forceinline__ bool quirk(int j, int K) const { return (rec[1] >> j) & 1u; }
-    __device__ __forceinline__ void load5(int j, int c, int K, uint32_t (&t5)[5]) const {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) t5[i] = at(j, c, K)[i];
-    }
-};
-// acc[j] ^= sum_c coef(j, c) * x[c] over one column, exact E rows, survivors already in registers
-template <int K, int E, int D>
-__device__ __forceinline__ void recon_mac_core(const uint32_t (&x)[K][D], uint32_t (&acc)[E][D], const RTab& T) {
-#pragma unroll
-    for (int c = 0; c + 1 < K; c += 2) {
-        Sel sa[D], sb[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) { sa[d] = gf_sel(x[c][d]); sb[d] = gf_sel(x[c + 1][d]); }
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            uint32_t a5[5], b5[5];
-            T.load5(j, c, K, a5);
-            T.load5(j, c + 1, K, b5);
-#pragma unroll
-            for (int d = 0; d < D; ++d) acc[j][d] = mac2(acc[j][d], sa[d], sb[d], a5, b5);
-        }
-    }
-    if (K & 1) {
-        Sel sl[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) sl[d] = gf_sel(x[K - 1][d]);
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            uint32_t t[5];
-            T.load5(j, K - 1, K, t);
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-                acc[j][d] = xor3(acc[j][d], pp0(sl[d], t[0], t[1]), pp1(sl[d], t[2], t[3])) ^ pp2(sl[d], t[4]);
-        }
-    }
 }
 
 template <int K, int E, int D>

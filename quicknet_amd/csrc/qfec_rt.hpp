@@ -9,6 +9,7 @@
 //   qfec_wire_api.cpp  the datagram / framing entry points (qfec_pack_*, qfec_unpack_*, ...)
 //   qfec_repair.cpp    qfec_repair (its LUT and records) and qfec_verify
 //   qfec_locate.cpp    qfec_locate (its ratio tables), qfec_scrub
+//   qfec_locate_erased.cpp  qfec_locate_erased (its LUT and records), qfec_scrub_erased
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -156,6 +157,9 @@ struct DevTables {
     uint64_t rep_version = ~0ull;
     uint32_t* d_loc = nullptr;      // [k][m-1][8] locate: perm tables of P[j][i] / P[0][i] (qfec_locate.cpp)
     uint64_t loc_version = ~0ull;
+    int32_t* d_le_lut = nullptr;    // [2^n] locate-erased: full n-bit mask -> record (qfec_locate_erased.cpp)
+    uint32_t* d_le_rec = nullptr;   // LocErasedLayout records
+    uint64_t le_version = ~0ull;
 };
 
 struct qfec_code {
@@ -173,6 +177,13 @@ struct qfec_code {
     // host-pointer reconstruct must stage the erased rows too (filled with the LUT)
     std::shared_ptr<const std::vector<uint8_t>> lut_seed;  // replaced whole on a rebuild; readers keep a reference
     uint64_t lut_seed_version = ~0ull;
+    // qfec_locate_erased's host tables (qfec_locate_erased.cpp): the records of every mask with
+    // t <= m - 1, or why the code is refused; built once per version under mu, uploaded per device
+    uint64_t le_host_version = ~0ull;
+    int le_rc = 0;
+    std::string le_error;
+    std::vector<uint32_t> le_recs;
+    std::vector<std::pair<uint32_t, int32_t>> le_masks;  // (mask, record offset in dwords)
 };
 
 namespace qfec {

@@ -301,6 +301,8 @@ void free_code(qfec_code* c) {
         if (kv.second.d_rep_lut) (void)hipFree(kv.second.d_rep_lut);
         if (kv.second.d_rep_rec) (void)hipFree(kv.second.d_rep_rec);
         if (kv.second.d_loc) (void)hipFree(kv.second.d_loc);
+        if (kv.second.d_le_lut) (void)hipFree(kv.second.d_le_lut);
+        if (kv.second.d_le_rec) (void)hipFree(kv.second.d_le_rec);
     }
     if (have) (void)hipSetDevice(prev);
     delete c;
