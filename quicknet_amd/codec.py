@@ -301,20 +301,31 @@ class Code:
             return t, None, None, None
         return t, rows[:t].copy(), surv, lost[:t].copy()
 
+    def _group_args(self, what, data, parity, block_size, out, out_name="culprit", counts=None, ncounts=0, marks=None):
+        """The checks verify / locate / scrub and the two erased calls share -> (G, block_size, pitch,
+        out): out is the call's per-group device int32 [G] result, allocated when not given; marks
+        (the erased calls' input) and counts are checked when given."""
+        import torch
+        G, k, pitch = data.shape
+        with_marks = "" if marks is None else f"marks {marks.numel()} "
+        if (k != self.k or tuple(parity.shape) != (G, self.m, pitch)
+                or (marks is not None and marks.numel() != G * (self.k + self.m))):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
+                            f"{with_marks}for ({self.k},{self.m})")
+        if out is None:
+            out = torch.empty(G, dtype=torch.int32, device=data.device)
+        elif out.numel() != G:
+            raise QfecError(f"{what}: {out_name} has {out.numel()} elements for {G} groups")
+        if counts is not None and counts.numel() != ncounts:
+            raise QfecError(f"{what}: counts has {counts.numel()} elements, not {ncounts}")
+        return G, pitch if block_size is None else block_size, pitch, out
+
     def verify(self, data, parity, block_size=None, bad_rows=None, bad_groups=None, stream=None):
         """Does parity[g] equal P x data[g] (qfec_verify)?  Returns bad_rows, a device int32 [G]
         tensor (allocated when not given): bit j set = parity row j of that group differs in some
         byte of [0, block_size); bad_groups: optional device int32/uint32 [1] counter that gains 1
         per inconsistent group (accumulates)."""
-        import torch
-        G, k, pitch = data.shape
-        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
-            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
-        if bad_rows is None:
-            bad_rows = torch.empty(G, dtype=torch.int32, device=data.device)
-        elif bad_rows.numel() != G:
-            raise QfecError(f"verify: bad_rows has {bad_rows.numel()} elements for {G} groups")
-        block_size = pitch if block_size is None else block_size
+        G, block_size, pitch, bad_rows = self._group_args("verify", data, parity, block_size, bad_rows, "bad_rows")
         check(lib().qfec_verify(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
                                 pitch, _dev_ptr(bad_rows, _I32, "bad_rows"), _dev_ptr(bad_groups, _I32, "bad_groups"),
                                 _stream_handle(stream)), "qfec_verify")
@@ -326,19 +337,11 @@ class Code:
         QFEC_LOC_MULTI (-2), QFEC_LOC_AMBIGUOUS (-3).  marks: optional device uint8 [G*k + G*m]
         (rs.c layout), written for every group: 1 at the culprit, else 0 -- ready for repair().
         counts: optional device int32/uint32 [3] located / multi / ambiguous (accumulates)."""
-        import torch
-        G, k, pitch = data.shape
-        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
-            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
-        if culprit is None:
-            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
-        elif culprit.numel() != G:
-            raise QfecError(f"locate: culprit has {culprit.numel()} elements for {G} groups")
+        G, block_size, pitch, culprit = self._group_args("locate", data, parity, block_size, culprit)
         if marks is not None and marks.numel() != G * (self.k + self.m):
             raise QfecError(f"locate: marks has {marks.numel()} elements for {G} groups of {self.k + self.m}")
         if counts is not None and counts.numel() != 3:
             raise QfecError(f"locate: counts has {counts.numel()} elements, not 3")
-        block_size = pitch if block_size is None else block_size
         check(lib().qfec_locate(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
                                 pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks, what="marks"),
                                 _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate")
@@ -348,17 +351,7 @@ class Code:
         """locate() + repair() of the located shard in one call (qfec_scrub): a group with one
         corrupted shard is rewritten to its original bytes, MULTI / AMBIGUOUS groups are left as
         they are and only reported.  Returns culprit as locate() does."""
-        import torch
-        G, k, pitch = data.shape
-        if k != self.k or tuple(parity.shape) != (G, self.m, pitch):
-            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
-        if culprit is None:
-            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
-        elif culprit.numel() != G:
-            raise QfecError(f"scrub: culprit has {culprit.numel()} elements for {G} groups")
-        if counts is not None and counts.numel() != 3:
-            raise QfecError(f"scrub: counts has {counts.numel()} elements, not 3")
-        block_size = pitch if block_size is None else block_size
+        G, block_size, pitch, culprit = self._group_args("scrub", data, parity, block_size, culprit, counts=counts, ncounts=3)
         check(lib().qfec_scrub(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
                                pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
                                _stream_handle(stream)), "qfec_scrub")
@@ -375,21 +368,6 @@ class Code:
     def prepare_locate_erased(self):
         check(lib().qfec_prepare_locate_erased(self._h), "qfec_prepare_locate_erased")
 
-    def _erased_args(self, what, data, parity, marks, culprit, counts):
-        import torch
-        G, k, pitch = data.shape
-        n = self.k + self.m
-        if k != self.k or tuple(parity.shape) != (G, self.m, pitch) or marks.numel() != G * n:
-            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
-                            f"marks {marks.numel()} for ({self.k},{self.m})")
-        if culprit is None:
-            culprit = torch.empty(G, dtype=torch.int32, device=data.device)
-        elif culprit.numel() != G:
-            raise QfecError(f"{what}: culprit has {culprit.numel()} elements for {G} groups")
-        if counts is not None and counts.numel() != 5:
-            raise QfecError(f"{what}: counts has {counts.numel()} elements, not 5")
-        return G, pitch, culprit
-
     def locate_erased(self, data, parity, marks, block_size=None, culprit=None, marks_out=None, counts=None,
                       stream=None):
         """Which single surviving shard of each group is corrupted, when groups also have lost shards
@@ -399,10 +377,10 @@ class Code:
         marks_out: optional device uint8 like marks (may be marks itself), written for every group:
         the marks as 0 / 1 plus 1 at a located culprit -- ready for repair().  counts: optional device
         int32/uint32 [5] located / multi / ambiguous / unchecked / lost (accumulates)."""
-        G, pitch, culprit = self._erased_args("locate_erased", data, parity, marks, culprit, counts)
+        G, block_size, pitch, culprit = self._group_args("locate_erased", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=5, marks=marks)
         if marks_out is not None and marks_out.numel() != marks.numel():
             raise QfecError(f"locate_erased: marks_out has {marks_out.numel()} elements, marks {marks.numel()}")
-        block_size = pitch if block_size is None else block_size
         check(lib().qfec_locate_erased(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
                                        _dev_ptr(marks, what="marks"), G, block_size, pitch,
                                        _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks_out, what="marks_out"),
@@ -415,8 +393,8 @@ class Code:
         LOST groups are left as they are and only reported; UNCHECKED groups and CLEAN groups with
         lost shards are repaired as repair() would.  failed: optional device int32/uint32 [1],
         repair()'s counter (the LOST groups).  Returns culprit as locate_erased() does."""
-        G, pitch, culprit = self._erased_args("scrub_erased", data, parity, marks, culprit, counts)
-        block_size = pitch if block_size is None else block_size
+        G, block_size, pitch, culprit = self._group_args("scrub_erased", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=5, marks=marks)
         check(lib().qfec_scrub_erased(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
                                       _dev_ptr(marks, what="marks"), G, block_size, pitch,
                                       _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),

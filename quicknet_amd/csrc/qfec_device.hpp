@@ -1,6 +1,7 @@
 // qfec_device.hpp -- device helpers shared by the HIP kernels of libqfec (gfx950).
 // GF(2^8) multiply by a constant four bytes per v_perm_b32 (see qfec_kernels.hip header),
-// streamed loads/stores, division by a runtime constant.
+// streamed loads/stores, division by a runtime constant, and the bodies the integrity kernels share
+// (qfec_verify.hip, qfec_locate.hip, qfec_locate_erased.hip): products, reports, counters, marks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -194,6 +195,138 @@ __device__ __forceinline__ uint4 column_mask(uint32_t block, uint32_t col) {
 
 __device__ __forceinline__ bool differs(const uint4& acc, const uint4& p, const uint4& mk) {
     return (((acc.x ^ p.x) & mk.x) | ((acc.y ^ p.y) & mk.y) | ((acc.z ^ p.z) & mk.z) | ((acc.w ^ p.w) & mk.w)) != 0;
+}
+
+// ------------------------------------------------------------------ P x data on the flat mapping
+// (qfec_verify.hip, qfec_locate.hip: one lane per 16-B column or per byte, the encode's perm tables)
+
+// compile-time K, M: acc[r] ^= sum_c P[r][c] x data row c, for the 16-B column at src.  For K >= 16
+// the inputs come in two halves, as in k_encode_perm_halves: half the input registers live at a time.
+// The parity loads stay with the caller, ahead of this: with them in here the RS(10,3) instances
+// come out at 61 VGPRs and 8 waves per SIMD where the loop written out in the kernel has 82 and 5.
+template <int K, int M>
+__device__ __forceinline__ void products16(uint4 (&acc)[M], const uint8_t* src, uint64_t pitch, const uint32_t* tab) {
+    constexpr int H = K >= 16 ? (K + 1) / 2 : K;
+#pragma unroll
+    for (int c0 = 0; c0 < K; c0 += H) {
+        if (H < K) __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
+        constexpr int HH = H;
+        const int n = min(HH, K - c0);
+        uint4 x[H];
+#pragma unroll
+        for (int i = 0; i < H; ++i)
+            if (i < n) x[i] = ld16(src + (uint64_t)(c0 + i) * pitch);
+#pragma unroll
+        for (int i = 0; i + 1 < H; i += 2) {
+            if (i + 1 >= n) continue;
+            Sel sa[4], sb[4];
+            sel16(sa, x[i]);
+            sel16(sb, x[i + 1]);
+#pragma unroll
+            for (int r = 0; r < M; ++r)
+                gf_mac16x2(acc[r], sa, sb, tab + (r * K + c0 + i) * QFEC_TAB_STRIDE,
+                           tab + (r * K + c0 + i + 1) * QFEC_TAB_STRIDE);
+        }
+        if (n & 1) {
+            Sel sl[4];
+            sel16(sl, x[n - 1]);
+#pragma unroll
+            for (int r = 0; r < M; ++r) gf_mac16(acc[r], sl, tab + (r * K + c0 + n - 1) * QFEC_TAB_STRIDE);
+        }
+    }
+}
+
+// runtime k, m: acc[j] = row r0 + j of the product, j < CH (rows past m stay zero); the k inputs are
+// re-read per chunk of CH rows (cache hits)
+template <int CH>
+__device__ __forceinline__ void products16_rows(uint4 (&acc)[CH], const uint8_t* src, uint64_t pitch,
+                                                const uint32_t* tab, int k, int m, int r0) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) acc[j] = make_uint4(0, 0, 0, 0);
+    for (int c = 0; c < k; ++c) {
+        const uint4 v = ld16(src + (uint64_t)c * pitch);
+        Sel s[4];
+        sel16(s, v);
+#pragma unroll
+        for (int j = 0; j < CH; ++j)
+            if (r0 + j < m) gf_mac16(acc[j], s, tab + ((r0 + j) * k + c) * QFEC_TAB_STRIDE);
+    }
+}
+
+// one byte of row r of the product (in the low byte; the rest is the product of zero bytes)
+__device__ __forceinline__ uint32_t product_byte(const uint8_t* src, uint64_t pitch, const uint32_t* tab, int k, int r) {
+    const uint32_t* tr = tab + (r * k) * QFEC_TAB_STRIDE;
+    uint32_t acc = 0;
+    for (int c = 0; c < k; ++c) {
+        const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
+        const Sel s = gf_sel((uint32_t)src[(uint64_t)c * pitch]);
+        acc ^= gf_mul4(s, tc[0], tc[1], tc[2], tc[3], tc[4]);
+    }
+    return acc;
+}
+
+// ------------------------------------------------------------------ reporting, off the hot path
+
+// A wave of the flat mapping reports its lanes' findings into the per-group words; every lane of the
+// wave calls it.  bad = this lane's row bits for group g (0 for idle lanes and clean columns).  Per
+// group seen in the wave the row bits are OR-reduced with ballots and one lane issues one atomic OR
+// into bad_rows[g] (preset to zero): a group's columns span waves and blocks.
+// CAND: cand = the shards that explain this lane's rows; AND-reduced likewise into cand_w[g] (preset
+// to all ones).  Without it, the OR that finds the word still zero counts the group in *bad_groups
+// (nullable), so a group is counted exactly once.
+template <bool CAND>
+__device__ __forceinline__ void flat_report(unsigned int* bad_rows, unsigned int* cand_w, unsigned int* bad_groups,
+                                            int k, int m, uint32_t g, uint32_t bad, uint32_t cand) {
+    uint64_t pending = __ballot(bad != 0);
+    const int lane = threadIdx.x & 63;
+    while (pending) {  // wave-uniform; one round per group with a finding in this wave
+        const int leader = __builtin_ctzll(pending);
+        const uint32_t gl = (uint32_t)__shfl((int)g, leader);
+        const bool same = bad != 0 && g == gl;
+        uint32_t rows = 0, keep = 0;
+        for (int j = 0; j < m; ++j)
+            if (__ballot(same && ((bad >> j) & 1u))) rows |= 1u << j;
+        if constexpr (CAND) {
+            for (int i = 0; i < k; ++i)
+                if (!__ballot(same && !((cand >> i) & 1u))) keep |= 1u << i;
+        }
+        if (lane == leader) {
+            const unsigned old = atomicOr(bad_rows + gl, rows);
+            if constexpr (CAND) atomicAnd(cand_w + gl, keep);
+            else if (old == 0 && bad_groups) atomicAdd(bad_groups, 1u);
+        }
+        pending &= ~__ballot(same);
+    }
+}
+
+// Every thread of a 256-thread block calls it with its verdict (a counter index, or -1 for none).
+// One add per block and counter, summed over the block's waves in LDS: adds on one address run one
+// after the other (about 10 ns each, measured), and with every group damaged an add per lane took
+// longer than the main kernel.
+template <int N>
+__device__ __forceinline__ void block_counts(int verdict, unsigned int* counts) {
+    __shared__ unsigned int sum[N];
+    if (threadIdx.x < N) sum[threadIdx.x] = 0;
+    __syncthreads();
+    for (int c = 0; c < N; ++c) {
+        const uint64_t hit = __ballot(verdict == c);
+        if (hit && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(hit)) atomicAdd(&sum[c], (unsigned)__builtin_popcountll(hit));
+    }
+    __syncthreads();
+    if (threadIdx.x < N && sum[threadIdx.x]) atomicAdd(counts + threadIdx.x, sum[threadIdx.x]);
+}
+
+// group g's marks from a mask over its k + m shards (k, m <= 32), in the rs.c layout: every group's
+// data marks, then every group's parity marks
+__device__ __forceinline__ void write_marks_rs(uint8_t* marks, uint64_t groups, uint64_t g, int k, int m, uint64_t mask) {
+    uint8_t* dm = marks + g * (uint64_t)k;
+    uint8_t* pm = marks + groups * (uint64_t)k + g * (uint64_t)m;
+    const uint32_t dmask = (uint32_t)mask, pmask = (uint32_t)(mask >> k);
+    // four marks per store: at the vectoriser's own width of 8 the shifted copies cost more registers
+#pragma clang loop vectorize_width(4)
+    for (int i = 0; i < k; ++i) dm[i] = (dmask >> i) & 1u;
+#pragma clang loop vectorize_width(4)
+    for (int j = 0; j < m; ++j) pm[j] = (pmask >> j) & 1u;
 }
 
 }  // namespace qfec

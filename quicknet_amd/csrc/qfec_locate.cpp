@@ -9,8 +9,7 @@
 
 namespace qfec {
 
-// Can single-shard location work on this code at all?  Decided on the host, before any device.
-static int locate_unsupported(const qfec_code* c, const char* who) {
+int locate_code_check(const qfec_code* c, const char* who, bool need_lut) {
     if (c->m < 2) {
         set_error("%s: m = %d < 2 (one parity row detects an error but cannot tell which shard holds it)", who, c->m);
         return QFEC_EUNSUP;
@@ -26,24 +25,28 @@ static int locate_unsupported(const qfec_code* c, const char* who) {
                           who, j, i);
                 return QFEC_EUNSUP;
             }
+    if (need_lut && c->k + c->m > QFEC_LUT_MAX_N) {
+        set_error("%s: k + m = %d > %d is not supported (the pattern LUT is keyed by the whole mask, as qfec_repair's)",
+                  who, c->k + c->m, QFEC_LUT_MAX_N);
+        return QFEC_EUNSUP;
+    }
     return QFEC_OK;
 }
 
-// r_{j,i} = P[j][i] / P[0][i] at [i * (m - 1) + (j - 1)], j = 1..m-1 (the code passed locate_unsupported)
-static void locate_ratios(const qfec_code* c, std::vector<uint8_t>& out) {
+void ratio_rows(const uint8_t* rows, int S, int k, std::vector<uint8_t>& out) {
     const Field& f = field();
-    const int k = c->k, m = c->m;
-    out.resize((size_t)k * (m - 1));
+    out.assign((size_t)k * (S - 1), 0);
     for (int i = 0; i < k; ++i)
-        for (int j = 1; j < m; ++j) out[(size_t)i * (m - 1) + (j - 1)] = f.mul[c->rows[(size_t)j * k + i]][f.inv[c->rows[i]]];
+        for (int x = 1; x < S; ++x) out[(size_t)i * (S - 1) + (x - 1)] = f.mul[rows[(size_t)x * k + i]][f.inv[rows[i]]];
 }
 
-// ratio perm tables of `c` on device `dev` (caller holds c->mu)
+// perm tables of r_{j,i} = P[j][i] / P[0][i] of `c` on device `dev` (caller holds c->mu; the code
+// passed locate_code_check)
 static int ensure_loc(qfec_code* c, int dev, uint32_t** out) {
     DevTables& d = c->dev[dev];
     if (d.loc_version != c->version || !d.d_loc) {
         std::vector<uint8_t> r;
-        locate_ratios(c, r);
+        ratio_rows(c->rows.data(), c->m, c->k, r);
         std::vector<uint32_t> t(r.size() * QFEC_TAB_STRIDE);
         for (size_t x = 0; x < r.size(); ++x) perm_entry(r[x], &t[x * QFEC_TAB_STRIDE]);
         if (d.d_loc) HIP_TRY(hipFree(d.d_loc));
@@ -68,18 +71,10 @@ static int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const
         if (!rc) rc = ensure_loc(code, ctx.device, &rtab);
     }
     if (rc) return rc;
-    // per-group working words from stream-ordered scratch: [groups] bad rows, then [groups] candidates
-    unsigned* words = nullptr;
-    if (hipMallocAsync((void**)&words, (size_t)groups * 8, s) != hipSuccess)
-        return hip_fail(hipGetLastError(), "locate scratch");
-    auto done = [&](int r) {
-        (void)hipFreeAsync(words, s);
-        return r;
-    };
-    unsigned *rows = words, *cand = words + groups;
-    hipError_t he = hipMemsetAsync(rows, 0, (size_t)groups * 4, s);
-    if (he == hipSuccess) he = hipMemsetAsync(cand, 0xFF, (size_t)groups * 4, s);
-    if (he != hipSuccess) return done(hip_fail(he, "locate: presetting the group words"));
+    GroupWords words(s);  // [groups] bad rows, then [groups] candidates
+    rc = words.init("locate", groups, 2);
+    if (rc) return rc;
+    unsigned *rows = words.at(0), *cand = words.at(1);
     LocateArgs a{};
     a.tab = tab;
     a.rtab = rtab;
@@ -89,21 +84,20 @@ static int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const
     a.block = (uint32_t)block_size;
     a.dgs = (uint64_t)code->k * pitch;
     a.pgs = (uint64_t)code->m * pitch;
-    a.vec16 = vec16_ok(d_data, d_parity, block_size, pitch) ? 1 : 0;
-    a.cols = a.vec16 ? (uint32_t)((block_size + 15) / 16) : (uint32_t)block_size;
-    a.cols_div = make_div_magic(a.cols);
-    // batches of >= 2^31 lanes go in several launches, as qfec_verify's
-    const long long per = std::max<long long>(1, (long long)(0x7FFFFFFFll / a.cols));
-    for (long long g0 = 0; g0 < groups; g0 += per) {
-        const long long gn = std::min(per, groups - g0);
+    const FlatGeom fg = flat_geom(d_data, d_parity, block_size, pitch, a.dgs, a.pgs);
+    a.vec16 = fg.vec16;
+    a.cols = fg.cols;
+    a.cols_div = make_div_magic(fg.cols);
+    rc = for_group_chunks(groups, fg.per, [&](long long g0, long long gn) {
         a.data = d_data + (size_t)g0 * a.dgs;
         a.parity = d_parity + (size_t)g0 * a.pgs;
         a.bad_rows = rows + g0;
         a.cand = cand + g0;
         a.work = (uint64_t)gn * a.cols;
-        he = launch_locate(a, s);
-        if (he != hipSuccess) return done(hip_fail(he, "locate kernel launch"));
-    }
+        const hipError_t he = launch_locate(a, s);
+        return he == hipSuccess ? QFEC_OK : hip_fail(he, "locate kernel launch");
+    });
+    if (rc) return rc;
     LocateFinishArgs f{};
     f.bad_rows = rows;
     f.cand = cand;
@@ -113,9 +107,23 @@ static int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const
     f.groups = (uint64_t)groups;
     f.k = code->k;
     f.m = code->m;
-    he = launch_locate_finish(f, s);
-    if (he != hipSuccess) return done(hip_fail(he, "locate finish kernel launch"));
-    return done(QFEC_OK);
+    const hipError_t he = launch_locate_finish(f, s);
+    return he == hipSuccess ? QFEC_OK : hip_fail(he, "locate finish kernel launch");
+}
+
+int run_scrub(const char* who, qfec_code* code, uint8_t* d_data, uint8_t* d_parity, long long groups, int block_size,
+              long long pitch, size_t extra, unsigned* d_failed, hipStream_t s,
+              const std::function<int(uint8_t* marks, uint8_t* extra)>& locate) {
+    int rc = qfec_prepare_repair(code);  // the repair LUT (synchronous on its first build) before the stream work
+    if (rc) return rc;
+    uint8_t* scratch = nullptr;
+    const size_t mark_bytes = round_up((size_t)groups * (size_t)(code->k + code->m), 16);
+    if (hipMallocAsync((void**)&scratch, mark_bytes + extra, s) != hipSuccess)
+        return hip_fail(hipGetLastError(), (std::string(who + 5) + " scratch").c_str());  // who less "qfec_"
+    rc = locate(scratch, scratch + mark_bytes);
+    if (!rc) rc = qfec_repair(code, d_data, d_parity, scratch, groups, block_size, pitch, d_failed, (void*)s);
+    (void)hipFreeAsync(scratch, s);
+    return rc;
 }
 
 }  // namespace qfec
@@ -126,10 +134,10 @@ extern "C" {
 
 int qfec_locate_ratios(const qfec_code* code, unsigned char* out) {
     if (!code || !out) return QFEC_EINVAL;
-    const int rc = locate_unsupported(code, "qfec_locate_ratios");
+    const int rc = locate_code_check(code, "qfec_locate_ratios", false);
     if (rc) return rc;
     std::vector<uint8_t> r;
-    locate_ratios(code, r);
+    ratio_rows(code->rows.data(), code->m, code->k, r);
     memcpy(out, r.data(), r.size());
     return QFEC_OK;
 }
@@ -137,51 +145,36 @@ int qfec_locate_ratios(const qfec_code* code, unsigned char* out) {
 int qfec_locate(qfec_code* code, const unsigned char* d_data, const unsigned char* d_parity, long long groups,
                 int block_size, long long pitch, int* d_culprit, unsigned char* d_marks, unsigned int* d_counts,
                 void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size ||
-        (groups > 0 && (!d_data || !d_parity || !d_culprit))) {
-        set_error("qfec_locate: invalid argument");
-        return QFEC_EINVAL;
-    }
-    int rc = locate_unsupported(code, "qfec_locate");
-    if (rc) return rc;
-    if (groups == 0) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    rc = current_ctx(&ctx);
-    if (rc) return rc;
+    const int rc = batch_begin(
+        "qfec_locate", bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || !d_parity || !d_culprit)),
+        [&] { return locate_code_check(code, "qfec_locate", false); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
     return run_locate(*ctx, code, d_data, d_parity, groups, block_size, pitch, d_culprit, d_marks, d_counts,
                       (hipStream_t)stream);
 }
 
 int qfec_scrub(qfec_code* code, unsigned char* d_data, unsigned char* d_parity, long long groups, int block_size,
                long long pitch, int* d_culprit, unsigned int* d_counts, void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size || (groups > 0 && (!d_data || !d_parity))) {
-        set_error("qfec_scrub: invalid argument");
-        return QFEC_EINVAL;
-    }
-    int rc = locate_unsupported(code, "qfec_scrub");
-    if (rc) return rc;
-    if (code->k + code->m > QFEC_LUT_MAX_N) {  // qfec_repair's limit, before anything is launched
-        set_error("qfec_scrub: k + m = %d > %d is not supported (qfec_repair's limit)", code->k + code->m, QFEC_LUT_MAX_N);
-        return QFEC_EUNSUP;
-    }
-    if (groups == 0) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    rc = current_ctx(&ctx);
-    if (rc) return rc;
-    rc = qfec_prepare_repair(code);  // the repair LUT (synchronous on its first build) before the stream work
-    if (rc) return rc;
+    const int rc = batch_begin(
+        "qfec_scrub", bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || !d_parity)),
+        [&] {
+            const int r = locate_code_check(code, "qfec_scrub", false);
+            if (r || code->k + code->m <= QFEC_LUT_MAX_N) return r;
+            // qfec_repair's limit, before anything is launched
+            set_error("qfec_scrub: k + m = %d > %d is not supported (qfec_repair's limit)", code->k + code->m, QFEC_LUT_MAX_N);
+            return QFEC_EUNSUP;
+        },
+        groups == 0, &ctx);
+    if (rc || !ctx) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)(code->k + code->m);
-    // stream-ordered scratch: the marks, and the verdicts when the caller does not want them
-    uint8_t* scratch = nullptr;
-    const size_t mark_bytes = round_up((size_t)groups * n, 16);
-    if (hipMallocAsync((void**)&scratch, mark_bytes + (d_culprit ? 0 : (size_t)groups * 4), s) != hipSuccess)
-        return hip_fail(hipGetLastError(), "scrub scratch");
-    int* culprit = d_culprit ? d_culprit : (int*)(scratch + mark_bytes);
-    rc = run_locate(*ctx, code, d_data, d_parity, groups, block_size, pitch, culprit, scratch, d_counts, s);
-    if (!rc) rc = qfec_repair(code, d_data, d_parity, scratch, groups, block_size, pitch, nullptr, stream);
-    (void)hipFreeAsync(scratch, s);
-    return rc;
+    // the verdicts come from the scratch too when the caller does not want them
+    return run_scrub("qfec_scrub", code, d_data, d_parity, groups, block_size, pitch, d_culprit ? 0 : (size_t)groups * 4,
+                     nullptr, s, [&](uint8_t* marks, uint8_t* extra) {
+                         return run_locate(*ctx, code, d_data, d_parity, groups, block_size, pitch,
+                                           d_culprit ? d_culprit : (int*)extra, marks, d_counts, s);
+                     });
 }
 
 }  // extern "C"

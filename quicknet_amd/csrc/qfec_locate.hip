@@ -42,32 +42,9 @@ __device__ __forceinline__ bool ratio_holds(const Sel (&s0)[4], const uint4& sj,
     return same16(pr, sj);
 }
 
-// Every lane of the wave calls it.  bad = this lane's syndrome bits for group g (0 for idle lanes
-// and clean columns), cand = the data shards that explain this lane's syndromes.
-__device__ __forceinline__ void locate_report(const LocateArgs& a, uint32_t g, uint32_t bad, uint32_t cand) {
-    uint64_t pending = __ballot(bad != 0);
-    const int lane = threadIdx.x & 63;
-    while (pending) {  // wave-uniform; one round per group with a non-zero syndrome in this wave
-        const int leader = __builtin_ctzll(pending);
-        const uint32_t gl = (uint32_t)__shfl((int)g, leader);
-        const bool same = bad != 0 && g == gl;
-        uint32_t rows = 0, keep = 0;
-        for (int j = 0; j < a.m; ++j)
-            if (__ballot(same && ((bad >> j) & 1u))) rows |= 1u << j;
-        for (int i = 0; i < a.k; ++i)
-            if (!__ballot(same && !((cand >> i) & 1u))) keep |= 1u << i;
-        if (lane == leader) {
-            atomicOr(a.bad_rows + gl, rows);
-            atomicAnd(a.cand + gl, keep);
-        }
-        pending &= ~__ballot(same);
-    }
-}
-
-// compile-time K, M (the instances of k_verify_perm)
+// compile-time K, M
 template <int K, int M>
 __global__ void __launch_bounds__(256) k_locate_perm(LocateArgs a) {
-    constexpr int H = K >= 16 ? (K + 1) / 2 : K;
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     uint32_t g32 = 0, bad = 0;
     uint4 acc[M];  // the products, then the syndromes
@@ -78,37 +55,10 @@ __global__ void __launch_bounds__(256) k_locate_perm(LocateArgs a) {
         const uint32_t col = (uint32_t)(t - g * (uint64_t)a.cols);
         const uint8_t* src = a.data + g * a.dgs + (uint64_t)col * 16u;
         const uint8_t* par = a.parity + g * a.pgs + (uint64_t)col * 16u;
-        const uint32_t* __restrict__ tab = a.tab;
         uint4 p[M];
 #pragma unroll
         for (int r = 0; r < M; ++r) p[r] = ld16(par + (uint64_t)r * a.pitch);
-#pragma unroll
-        for (int c0 = 0; c0 < K; c0 += H) {
-            if (H < K) __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
-            constexpr int HH = H;
-            const int n = min(HH, K - c0);
-            uint4 x[H];
-#pragma unroll
-            for (int i = 0; i < H; ++i)
-                if (i < n) x[i] = ld16(src + (uint64_t)(c0 + i) * a.pitch);
-#pragma unroll
-            for (int i = 0; i + 1 < H; i += 2) {
-                if (i + 1 >= n) continue;
-                Sel sa[4], sb[4];
-                sel16(sa, x[i]);
-                sel16(sb, x[i + 1]);
-#pragma unroll
-                for (int r = 0; r < M; ++r)
-                    gf_mac16x2(acc[r], sa, sb, tab + (r * K + c0 + i) * QFEC_TAB_STRIDE,
-                               tab + (r * K + c0 + i + 1) * QFEC_TAB_STRIDE);
-            }
-            if (n & 1) {
-                Sel sl[4];
-                sel16(sl, x[n - 1]);
-#pragma unroll
-                for (int r = 0; r < M; ++r) gf_mac16(acc[r], sl, tab + (r * K + c0 + n - 1) * QFEC_TAB_STRIDE);
-            }
-        }
+        products16<K, M>(acc, src, a.pitch, a.tab);
         const uint4 mk = column_mask(a.block, col);
 #pragma unroll
         for (int r = 0; r < M; ++r) {
@@ -132,10 +82,10 @@ __global__ void __launch_bounds__(256) k_locate_perm(LocateArgs a) {
             if (ok) cand |= 1u << i;
         }
     }
-    locate_report(a, g32, bad, cand);
+    flat_report<true>(a.bad_rows, a.cand, nullptr, a.k, a.m, g32, bad, cand);
 }
 
-// runtime k, m: rows in chunks of LCH, the k inputs re-read per chunk (cache hits), as k_verify_any.
+// runtime k, m: rows in chunks of LCH.
 // s_0 comes with the first chunk and stays; each chunk's rows are tested against it while they
 // are live.  A lane whose first non-zero syndrome turns up in a later chunk has s_0 = 0 there, and
 // the test of that chunk then drops every candidate, as it must.
@@ -162,14 +112,7 @@ __global__ void __launch_bounds__(256) k_locate_any(LocateArgs a) {
 #pragma unroll
         for (int j = 0; j < LCH; ++j) s[j] = make_uint4(0, 0, 0, 0);
         if (live) {
-            for (int c = 0; c < k; ++c) {
-                const uint4 v = ld16(src + (uint64_t)c * a.pitch);
-                Sel sl[4];
-                sel16(sl, v);
-#pragma unroll
-                for (int j = 0; j < LCH; ++j)
-                    if (r0 + j < m) gf_mac16(s[j], sl, a.tab + ((r0 + j) * k + c) * QFEC_TAB_STRIDE);
-            }
+            products16_rows<LCH>(s, src, a.pitch, a.tab, k, m, r0);
 #pragma unroll
             for (int j = 0; j < LCH; ++j)
                 if (r0 + j < m) {
@@ -195,7 +138,7 @@ __global__ void __launch_bounds__(256) k_locate_any(LocateArgs a) {
         }
     }
     if (__ballot(bad != 0) == 0) return;
-    locate_report(a, g32, bad, cand);
+    flat_report<true>(a.bad_rows, a.cand, nullptr, a.k, a.m, g32, bad, cand);
 }
 
 // byte-granular fallback for pitches / pointers that are not 16-B aligned: one lane per byte of
@@ -218,14 +161,7 @@ __global__ void __launch_bounds__(256) k_locate_bytes(LocateArgs a) {
     for (int r = 0; r < m; ++r) {  // wave-uniform
         uint32_t s = 0;
         if (live) {
-            const uint32_t* tr = a.tab + (r * k) * QFEC_TAB_STRIDE;
-            uint32_t acc = 0;
-            for (int c = 0; c < k; ++c) {
-                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
-                const Sel sl = gf_sel((uint32_t)src[(uint64_t)c * a.pitch]);
-                acc ^= gf_mul4(sl, tc[0], tc[1], tc[2], tc[3], tc[4]);
-            }
-            s = (acc ^ (uint32_t)par[(uint64_t)r * a.pitch]) & 0xFFu;
+            s = (product_byte(src, a.pitch, a.tab, k, r) ^ (uint32_t)par[(uint64_t)r * a.pitch]) & 0xFFu;
             if (s) bad |= 1u << r;
             if (r == 0) s0 = s;
         }
@@ -239,7 +175,7 @@ __global__ void __launch_bounds__(256) k_locate_bytes(LocateArgs a) {
         }
     }
     if (__ballot(bad != 0) == 0) return;
-    locate_report(a, g32, bad, cand);
+    flat_report<true>(a.bad_rows, a.cand, nullptr, a.k, a.m, g32, bad, cand);
 }
 
 // the verdict of group g from its two words: candidates = the data bits that survived every column,
@@ -256,12 +192,7 @@ __device__ __forceinline__ int locate_verdict(const LocateFinishArgs& a, uint64_
         id = nc == 0 ? QFEC_LOC_MULTI : nc > 1 ? QFEC_LOC_AMBIGUOUS : dc ? __builtin_ctz(dc) : k + __builtin_ctz(rows);
     }
     a.culprit[g] = id;
-    if (a.marks) {
-        uint8_t* dm = a.marks + g * (uint64_t)k;  // rs.c layout: every group's data marks, then the parity marks
-        uint8_t* pm = a.marks + a.groups * (uint64_t)k + g * (uint64_t)m;
-        for (int i = 0; i < k; ++i) dm[i] = i == id ? 1 : 0;
-        for (int j = 0; j < m; ++j) pm[j] = k + j == id ? 1 : 0;
-    }
+    if (a.marks) write_marks_rs(a.marks, a.groups, g, k, m, id >= 0 ? 1ull << id : 0ull);
     return rows == 0 ? -1 : id >= 0 ? 0 : id == QFEC_LOC_MULTI ? 1 : 2;
 }
 
@@ -270,19 +201,7 @@ __global__ void __launch_bounds__(256) k_locate_finish(LocateFinishArgs a) {
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     int verdict = -1;  // also for lanes past the last group
     if (g < a.groups) verdict = locate_verdict(a, g);
-    if (!a.counts) return;  // uniform over the grid
-    // one add per block and counter, summed over the block's waves in LDS: adds on one address
-    // run one after the other (about 10 ns each, measured), and with every group damaged an add
-    // per lane took longer than the main kernel
-    __shared__ unsigned int sum[3];
-    if (threadIdx.x < 3) sum[threadIdx.x] = 0;
-    __syncthreads();
-    for (int c = 0; c < 3; ++c) {
-        const uint64_t hit = __ballot(verdict == c);
-        if (hit && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(hit)) atomicAdd(&sum[c], (unsigned)__builtin_popcountll(hit));
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && sum[threadIdx.x]) atomicAdd(a.counts + threadIdx.x, sum[threadIdx.x]);
+    if (a.counts) block_counts<3>(verdict, a.counts);  // uniform over the grid
 }
 
 #define QFEC_LOC_CASE(KK, MM)                                                                    \
@@ -300,7 +219,7 @@ hipError_t launch_locate(const LocateArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(k_locate_bytes, dim3(grid), dim3(256), 0, stream, a);
         return hipGetLastError();
     }
-    // verify's instances with m >= 2 (qfec_verify.hip, launch_verify)
+    // launch_verify's instances with m >= 2
     QFEC_LOC_CASE(10, 3)
     QFEC_LOC_CASE(16, 4)
     QFEC_LOC_CASE(4, 2)

@@ -8,7 +8,7 @@
 // those of the code punctured at E.  Per code there is one record per mask with t <= m - 1 (the ids
 // of K and R, the table offsets of A and of the ratios A_x[i] / A_0[i]), built on the host once per
 // code->version under code->mu -- building them is also the check that the punctured codes are MDS
-// -- and a 2^n-entry LUT from the mask to its record per device, like the repair's.
+// -- and a 2^n-entry LUT from the mask to its record per device (a DevLut).
 #include "qfec_rt.hpp"
 
 namespace qfec {
@@ -23,31 +23,6 @@ LocErasedLayout loc_erased_layout(int k, int m) {
 }
 
 constexpr size_t kErasedMaxTableBytes = (size_t)256 << 20;  // the records of one code
-
-// everything qfec_locate refuses, and the LUT's key width
-static int erased_unsupported(const qfec_code* c, const char* who) {
-    if (c->m < 2) {
-        set_error("%s: m = %d < 2 (one parity row detects an error but cannot tell which shard holds it)", who, c->m);
-        return QFEC_EUNSUP;
-    }
-    if (c->k > 32 || c->m > 32) {
-        set_error("%s: k = %d, m = %d: more than 32 (one candidate bit per shard in a 32-bit word)", who, c->k, c->m);
-        return QFEC_EUNSUP;
-    }
-    for (int j = 0; j < c->m; ++j)
-        for (int i = 0; i < c->k; ++i)
-            if (c->rows[(size_t)j * c->k + i] == 0) {
-                set_error("%s: parity row %d has a zero coefficient at data shard %d (an error there would not show in that row)",
-                          who, j, i);
-                return QFEC_EUNSUP;
-            }
-    if (c->k + c->m > QFEC_LUT_MAX_N) {
-        set_error("%s: k + m = %d > %d is not supported (the pattern LUT is keyed by the whole mask, as qfec_repair's)",
-                  who, c->k + c->m, QFEC_LUT_MAX_N);
-        return QFEC_EUNSUP;
-    }
-    return QFEC_OK;
-}
 
 // The plan of one group-order mark vector: survivors (k) = K, spares (S) = R, rows (S x k) = A,
 // ratios (k x (S - 1)) = A_x[i] / A_0[i] at [i*(S-1) + (x-1)] (0 where A_0[i] is 0).  Returns
@@ -78,15 +53,12 @@ static int erased_plan(const uint8_t* P, int k, int m, const uint8_t* marks, std
         const size_t r = std::find(lost.begin(), lost.end(), spares[x]) - lost.begin();
         memcpy(&rows[(size_t)x * k], &all[r * k], (size_t)k);
     }
-    const Field& f = field();
-    ratios.assign((size_t)k * (S - 1), 0);
-    for (int i = 0; i < k; ++i)
-        for (int x = 1; x < S; ++x) ratios[(size_t)i * (S - 1) + (x - 1)] = f.mul[rows[(size_t)x * k + i]][f.inv[rows[i]]];
+    ratio_rows(rows.data(), S, k, ratios);
     return S;
 }
 
 // the records of every mask with t <= m - 1, or the refusal (caller holds c->mu; the code passed
-// erased_unsupported).  Sets the error text on a refusal.
+// locate_code_check with need_lut).  Sets the error text on a refusal.
 static int ensure_erased_host(qfec_code* c, const char* who) {
     if (c->le_host_version != c->version) {
         const int k = c->k, m = c->m, n = k + m;
@@ -158,7 +130,7 @@ static int ensure_erased_host(qfec_code* c, const char* who) {
 }
 
 static int erased_supported(qfec_code* c, const char* who) {
-    const int rc = erased_unsupported(c, who);
+    const int rc = locate_code_check(c, who, true);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     return ensure_erased_host(c, who);
@@ -168,7 +140,7 @@ static int erased_supported(qfec_code* c, const char* who) {
 static int ensure_erased_lut(qfec_code* c, int dev, DevTables** out) {
     DevTables& d = c->dev[dev];
     *out = &d;
-    if (d.le_version == c->version && d.d_le_lut) return QFEC_OK;
+    if (d.le.version == c->version && d.le.lut) return QFEC_OK;
     const int m = c->m, n = c->k + c->m;
     const size_t nmask = (size_t)1 << n;
     std::vector<int32_t> lut(nmask);
@@ -177,16 +149,7 @@ static int ensure_erased_lut(qfec_code* c, int dev, DevTables** out) {
         lut[mask] = t > m ? QFEC_LE_LOST : QFEC_LE_UNCHECKED;  // t < m is overwritten below
     }
     for (const auto& e : c->le_masks) lut[e.first] = e.second;
-    if (d.d_le_lut) HIP_TRY(hipFree(d.d_le_lut));
-    if (d.d_le_rec) HIP_TRY(hipFree(d.d_le_rec));
-    d.d_le_lut = nullptr;
-    d.d_le_rec = nullptr;
-    HIP_TRY(hipMalloc(&d.d_le_lut, nmask * 4));
-    HIP_TRY(hipMalloc(&d.d_le_rec, std::max<size_t>(c->le_recs.size(), 8) * 4));
-    HIP_TRY(hipMemcpy(d.d_le_lut, lut.data(), nmask * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.d_le_rec, c->le_recs.data(), c->le_recs.size() * 4, hipMemcpyHostToDevice));
-    d.le_version = c->version;
-    return QFEC_OK;
+    return upload_lut(d.le, lut, c->le_recs, c->version);
 }
 
 // the launches of one qfec_locate_erased: two presets, the main kernel per chunk, the finish kernel
@@ -201,22 +164,14 @@ static int run_locate_erased(DevCtx& ctx, qfec_code* code, const uint8_t* d_data
         if (!rc) rc = ensure_erased_lut(code, ctx.device, &d);
     }
     if (rc) return rc;
-    // per-group working words from stream-ordered scratch: [groups] bad spares, then [groups] candidates
-    unsigned* words = nullptr;
-    if (hipMallocAsync((void**)&words, (size_t)groups * 8, s) != hipSuccess)
-        return hip_fail(hipGetLastError(), "locate_erased scratch");
-    auto done = [&](int r) {
-        (void)hipFreeAsync(words, s);
-        return r;
-    };
-    unsigned *bad = words, *cand = words + groups;
-    hipError_t he = hipMemsetAsync(bad, 0, (size_t)groups * 4, s);
-    if (he == hipSuccess) he = hipMemsetAsync(cand, 0xFF, (size_t)groups * 4, s);
-    if (he != hipSuccess) return done(hip_fail(he, "locate_erased: presetting the group words"));
+    GroupWords words(s);  // [groups] bad spares, then [groups] candidates
+    rc = words.init("locate_erased", groups, 2);
+    if (rc) return rc;
+    unsigned *bad = words.at(0), *cand = words.at(1);
     const LocErasedLayout L = loc_erased_layout(code->k, code->m);
     LocErasedArgs a{};
-    a.lut = d->d_le_lut;
-    a.records = d->d_le_rec;
+    a.lut = d->le.lut;
+    a.records = d->le.rec;
     a.t256 = ctx.d_t256;
     a.pitch = (uint64_t)pitch;
     a.block = (uint32_t)block_size;
@@ -227,15 +182,13 @@ static int run_locate_erased(DevCtx& ctx, qfec_code* code, const uint8_t* d_data
     a.roff = L.roff;
     a.dgs = (uint64_t)code->k * pitch;
     a.pgs = (uint64_t)code->m * pitch;
-    a.vec16 = vec16_ok(d_data, d_parity, block_size, pitch) ? 1 : 0;
-    a.cols = a.vec16 ? (uint32_t)((block_size + 15) / 16) : (uint32_t)block_size;
-    // 8-B columns as the repair's (run_repair): the 16-B columns' span for k < 14, else just the row
-    a.cols8 = a.vec16 && code->k < 14 ? 2u * a.cols : (uint32_t)((block_size + 7) / 8);
-    a.wpg8 = (a.cols8 + 63) / 64;
-    // batches of >= 2^31 lanes go in several launches, as the repair's
-    const long long per = std::max<long long>(1, 0x7FFFFFFFll / (64ll * (long long)std::max(a.wpg8, 1u)));
-    for (long long g0 = 0; g0 < groups; g0 += per) {
-        const long long gn = std::min(per, groups - g0);
+    const FlatGeom fg = flat_geom(d_data, d_parity, block_size, pitch, a.dgs, a.pgs);
+    const Lane8Geom l8 = lane8_geom(fg, code->k, block_size);
+    a.vec16 = fg.vec16;
+    a.cols = fg.cols;
+    a.cols8 = l8.cols8;
+    a.wpg8 = l8.wpg8;
+    rc = for_group_chunks(groups, l8.per, [&](long long g0, long long gn) {
         a.data = d_data + (size_t)g0 * a.dgs;
         a.parity = d_parity + (size_t)g0 * a.pgs;
         a.dmarks = d_marks + (size_t)g0 * code->k;  // rs.c layout: every group's data marks, then the parity marks
@@ -243,13 +196,14 @@ static int run_locate_erased(DevCtx& ctx, qfec_code* code, const uint8_t* d_data
         a.bad = bad + g0;
         a.cand = cand + g0;
         a.groups = (uint64_t)gn;
-        he = launch_locate_erased(a, s);
-        if (he != hipSuccess) return done(hip_fail(he, "locate_erased kernel launch"));
-    }
+        const hipError_t he = launch_locate_erased(a, s);
+        return he == hipSuccess ? QFEC_OK : hip_fail(he, "locate_erased kernel launch");
+    });
+    if (rc) return rc;
     LocErasedFinishArgs f{};
     f.marks = d_marks;
-    f.lut = d->d_le_lut;
-    f.records = d->d_le_rec;
+    f.lut = d->le.lut;
+    f.records = d->le.rec;
     f.bad = bad;
     f.cand = cand;
     f.culprit = d_culprit;
@@ -260,9 +214,8 @@ static int run_locate_erased(DevCtx& ctx, qfec_code* code, const uint8_t* d_data
     f.m = code->m;
     f.ids_off = L.ids_off;
     f.scrub = scrub;
-    he = launch_locate_erased_finish(f, s);
-    if (he != hipSuccess) return done(hip_fail(he, "locate_erased finish kernel launch"));
-    return done(QFEC_OK);
+    const hipError_t he = launch_locate_erased_finish(f, s);
+    return he == hipSuccess ? QFEC_OK : hip_fail(he, "locate_erased finish kernel launch");
 }
 
 }  // namespace qfec
@@ -306,17 +259,12 @@ int qfec_prepare_locate_erased(qfec_code* code) {
 int qfec_locate_erased(qfec_code* code, const unsigned char* d_data, const unsigned char* d_parity,
                        const unsigned char* d_marks, long long groups, int block_size, long long pitch, int* d_culprit,
                        unsigned char* d_marks_out, unsigned int* d_counts, void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size ||
-        (groups > 0 && (!d_data || !d_parity || !d_marks || !d_culprit))) {
-        set_error("qfec_locate_erased: invalid argument");
-        return QFEC_EINVAL;
-    }
-    int rc = erased_supported(code, "qfec_locate_erased");
-    if (rc) return rc;
-    if (groups == 0) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    rc = current_ctx(&ctx);
-    if (rc) return rc;
+    const int rc = batch_begin(
+        "qfec_locate_erased",
+        bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || !d_parity || !d_marks || !d_culprit)),
+        [&] { return erased_supported(code, "qfec_locate_erased"); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
     return run_locate_erased(*ctx, code, d_data, d_parity, d_marks, groups, block_size, pitch, d_culprit, d_marks_out,
                              d_counts, 0, (hipStream_t)stream);
 }
@@ -324,29 +272,17 @@ int qfec_locate_erased(qfec_code* code, const unsigned char* d_data, const unsig
 int qfec_scrub_erased(qfec_code* code, unsigned char* d_data, unsigned char* d_parity, const unsigned char* d_marks,
                       long long groups, int block_size, long long pitch, int* d_culprit, unsigned int* d_counts,
                       unsigned int* d_failed, void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size ||
-        (groups > 0 && (!d_data || !d_parity || !d_marks))) {
-        set_error("qfec_scrub_erased: invalid argument");
-        return QFEC_EINVAL;
-    }
-    int rc = erased_supported(code, "qfec_scrub_erased");
-    if (rc) return rc;
-    if (groups == 0) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    rc = current_ctx(&ctx);
-    if (rc) return rc;
-    rc = qfec_prepare_repair(code);  // the repair LUT (synchronous on its first build) before the stream work
-    if (rc) return rc;
+    const int rc = batch_begin(
+        "qfec_scrub_erased", bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || !d_parity || !d_marks)),
+        [&] { return erased_supported(code, "qfec_scrub_erased"); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // stream-ordered scratch: the marks that go to qfec_repair
-    uint8_t* scratch = nullptr;
-    if (hipMallocAsync((void**)&scratch, (size_t)groups * (size_t)(code->k + code->m), s) != hipSuccess)
-        return hip_fail(hipGetLastError(), "scrub_erased scratch");
-    rc = run_locate_erased(*ctx, code, d_data, d_parity, d_marks, groups, block_size, pitch, d_culprit, scratch, d_counts, 1,
-                           s);
-    if (!rc) rc = qfec_repair(code, d_data, d_parity, scratch, groups, block_size, pitch, d_failed, stream);
-    (void)hipFreeAsync(scratch, s);
-    return rc;
+    return run_scrub("qfec_scrub_erased", code, d_data, d_parity, groups, block_size, pitch, 0, d_failed, s,
+                     [&](uint8_t* marks, uint8_t*) {
+                         return run_locate_erased(*ctx, code, d_data, d_parity, d_marks, groups, block_size, pitch, d_culprit,
+                                                  marks, d_counts, 1, s);
+                     });
 }
 
 }  // extern "C"

@@ -319,10 +319,7 @@ __device__ __forceinline__ int erased_verdict(const LocErasedFinishArgs& a, uint
         // must stay as it is (marks_out may be marks: this lane alone touches group g's bytes)
         if (a.scrub && (id == QFEC_LOC_MULTI || id == QFEC_LOC_AMBIGUOUS)) mask = 0;
         if (id >= 0) mask |= 1u << id;
-        uint8_t* dmo = a.marks_out + g * (uint64_t)k;
-        uint8_t* pmo = a.marks_out + a.groups * (uint64_t)k + g * (uint64_t)m;
-        for (int i = 0; i < k; ++i) dmo[i] = (mask >> i) & 1u;
-        for (int j = 0; j < m; ++j) pmo[j] = (mask >> (k + j)) & 1u;
+        write_marks_rs(a.marks_out, a.groups, g, k, m, mask);
     }
     return id >= 0 ? 0 : id == QFEC_LOC_CLEAN ? -1 : -id - 1;  // MULTI -2 -> 1 ... LOST -5 -> 4
 }
@@ -332,17 +329,7 @@ __global__ void __launch_bounds__(256) k_locate_erased_finish(LocErasedFinishArg
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     int verdict = -1;  // also for lanes past the last group
     if (g < a.groups) verdict = erased_verdict(a, g);
-    if (!a.counts) return;  // uniform over the grid
-    // one add per block and counter, summed over the block's waves in LDS (k_locate_finish measured why)
-    __shared__ unsigned int sum[5];
-    if (threadIdx.x < 5) sum[threadIdx.x] = 0;
-    __syncthreads();
-    for (int c = 0; c < 5; ++c) {
-        const uint64_t hit = __ballot(verdict == c);
-        if (hit && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(hit)) atomicAdd(&sum[c], (unsigned)__builtin_popcountll(hit));
-    }
-    __syncthreads();
-    if (threadIdx.x < 5 && sum[threadIdx.x]) atomicAdd(a.counts + threadIdx.x, sum[threadIdx.x]);
+    if (a.counts) block_counts<5>(verdict, a.counts);  // uniform over the grid
 }
 
 // the repair's instances with m >= 2, the same launch shapes (qfec_kernels.hip, launch_repair)

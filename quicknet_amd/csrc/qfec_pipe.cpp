@@ -254,7 +254,7 @@ int qfec_pipe_reconstruct(qfec_pipe* p, qfec_code* code, unsigned char* h_data, 
                 rc = hip_fail(hipGetLastError(), "qfec_pipe_reconstruct: marks H2D");
                 break;
             }
-            if ((rc = run_reconstruct(*s->ctx, code, d->d_lut, nullptr, d->d_rec, z_data + (size_t)g0 * dg,
+            if ((rc = run_reconstruct(*s->ctx, code, d->dec.lut, nullptr, d->dec.rec, z_data + (size_t)g0 * dg,
                                       m ? z_par + (size_t)g0 * pg : nullptr, dm, gn, block_size, pitch, s->d_failed,
                                       s->stream)))
                 break;
@@ -273,7 +273,7 @@ int qfec_pipe_reconstruct(qfec_pipe* p, qfec_code* code, unsigned char* h_data, 
             rc = hip_fail(hipGetLastError(), "qfec_pipe_reconstruct: H2D");
             break;
         }
-        if ((rc = run_reconstruct(*s->ctx, code, d->d_lut, nullptr, d->d_rec, dd, dp, dm, gn, block_size, pitch,
+        if ((rc = run_reconstruct(*s->ctx, code, d->dec.lut, nullptr, d->dec.rec, dd, dp, dm, gn, block_size, pitch,
                                   s->d_failed, s->stream)))
             break;
         if (hipMemcpyAsync(h_data + (size_t)g0 * dg, dd, (size_t)gn * dg, hipMemcpyDeviceToHost, s->stream) !=

@@ -14,7 +14,7 @@ namespace qfec {
 static int ensure_repair_lut(qfec_code* c, int dev, DevTables** out) {
     DevTables& d = c->dev[dev];
     *out = &d;
-    if (d.rep_version == c->version && d.d_rep_lut) return QFEC_OK;
+    if (d.rep.version == c->version && d.rep.lut) return QFEC_OK;
     const int k = c->k, m = c->m, n = k + m;
     const size_t nmask = (size_t)1 << n;
     const RecordLayout L = record_layout(k, m);
@@ -37,16 +37,7 @@ static int ensure_repair_lut(qfec_code* c, int dev, DevTables** out) {
         build_repair_record(L, k, t, e, rows.data(), surv.data(), lost.data(), c->quirk != 0, &recs[off]);
         lut[mask] = (int32_t)off;
     }
-    if (d.d_rep_lut) HIP_TRY(hipFree(d.d_rep_lut));
-    if (d.d_rep_rec) HIP_TRY(hipFree(d.d_rep_rec));
-    d.d_rep_lut = nullptr;
-    d.d_rep_rec = nullptr;
-    HIP_TRY(hipMalloc(&d.d_rep_lut, nmask * 4));
-    HIP_TRY(hipMalloc(&d.d_rep_rec, std::max<size_t>(recs.size(), 8) * 4));
-    HIP_TRY(hipMemcpy(d.d_rep_lut, lut.data(), nmask * 4, hipMemcpyHostToDevice));
-    if (!recs.empty()) HIP_TRY(hipMemcpy(d.d_rep_rec, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
-    d.rep_version = c->version;
-    return QFEC_OK;
+    return upload_lut(d.rep, lut, recs, c->version);
 }
 
 static int repair_unsupported(const qfec_code* c) {
@@ -60,8 +51,8 @@ static int run_repair(DevCtx& ctx, const qfec_code* c, const DevTables& d, uint8
                       hipStream_t s) {
     RepairArgs a{};
     const RecordLayout L = record_layout(c->k, c->m);
-    a.lut = d.d_rep_lut;
-    a.records = d.d_rep_rec;
+    a.lut = d.rep.lut;
+    a.records = d.rep.rec;
     a.t256 = ctx.d_t256;
     a.failed = d_failed;
     a.pitch = (uint64_t)pitch;
@@ -72,24 +63,21 @@ static int run_repair(DevCtx& ctx, const qfec_code* c, const DevTables& d, uint8
     a.coff = L.coff;
     a.dgs = (uint64_t)c->k * pitch;
     a.pgs = (uint64_t)c->m * pitch;
-    a.vec16 = vec16_ok(d_data, d_par, block, pitch) ? 1 : 0;
-    a.cols = a.vec16 ? (uint32_t)((block + 15) / 16) : (uint32_t)block;
-    // 8-B columns: the 16-B columns' span for k < 14, else just the row (as the reconstruct, whose
-    // measurements this follows: qfec_runtime.cpp run_reconstruct)
-    a.cols8 = a.vec16 && c->k < 14 ? 2u * a.cols : (uint32_t)((block + 7) / 8);
-    a.wpg8 = (a.cols8 + 63) / 64;
-    const long long per = std::max<long long>(1, 0x7FFFFFFFll / (long long)std::max(a.wpg8, 1u));
-    for (long long g0 = 0; g0 < groups; g0 += per) {
-        const long long gn = std::min(per, groups - g0);
+    const FlatGeom f = flat_geom(d_data, d_par, block, pitch, a.dgs, a.pgs);
+    const Lane8Geom l8 = lane8_geom(f, c->k, block);
+    a.vec16 = f.vec16;
+    a.cols = f.cols;
+    a.cols8 = l8.cols8;
+    a.wpg8 = l8.wpg8;
+    return for_group_chunks(groups, l8.per, [&](long long g0, long long gn) {
         a.data = d_data + (size_t)g0 * a.dgs;
         a.parity = d_par + (size_t)g0 * a.pgs;
         a.dmarks = d_marks + (size_t)g0 * c->k;  // rs.c layout: every group's data marks, then the parity marks
         a.pmarks = d_marks + (size_t)groups * c->k + (size_t)g0 * c->m;
         a.groups = (uint64_t)gn;
-        hipError_t e = launch_repair(a, s);
-        if (e != hipSuccess) return hip_fail(e, "repair kernel launch");
-    }
-    return QFEC_OK;
+        const hipError_t e = launch_repair(a, s);
+        return e == hipSuccess ? QFEC_OK : hip_fail(e, "repair kernel launch");
+    });
 }
 
 }  // namespace qfec
@@ -111,16 +99,12 @@ int qfec_prepare_repair(qfec_code* code) {
 
 int qfec_repair(qfec_code* code, unsigned char* d_data, unsigned char* d_parity, const unsigned char* d_marks,
                 long long groups, int block_size, long long pitch, unsigned int* d_failed, void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size ||
-        (groups > 0 && (!d_data || !d_marks || (code->m > 0 && !d_parity)))) {
-        set_error("qfec_repair: invalid argument");
-        return QFEC_EINVAL;
-    }
-    if (code->k + code->m > QFEC_LUT_MAX_N) return repair_unsupported(code);
-    if (groups == 0) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    int rc = current_ctx(&ctx);
-    if (rc) return rc;
+    int rc = batch_begin(
+        "qfec_repair",
+        bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || !d_marks || (code->m > 0 && !d_parity))),
+        [&] { return code->k + code->m > QFEC_LUT_MAX_N ? repair_unsupported(code) : QFEC_OK; }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
     DevTables* d = nullptr;
     {
         std::lock_guard<std::mutex> lk(code->mu);
@@ -148,38 +132,28 @@ int qfec_repair_rows(const qfec_code* code, const unsigned char* marks_n, unsign
 int qfec_verify(qfec_code* code, const unsigned char* d_data, const unsigned char* d_parity, long long groups,
                 int block_size, long long pitch, unsigned int* d_bad_rows, unsigned int* d_bad_groups,
                 void* stream) {
-    if (!code || groups < 0 || block_size < 1 || pitch < block_size ||
-        (groups > 0 && (!d_data || (code->m > 0 && !d_parity)))) {
-        set_error("qfec_verify: invalid argument");
-        return QFEC_EINVAL;
-    }
-    if (code->m > 32) {
-        set_error("qfec_verify: m = %d > 32 (one bit per parity row in a 32-bit word)", code->m);
-        return QFEC_EUNSUP;
-    }
-    if (groups == 0 || (!d_bad_rows && !d_bad_groups)) return QFEC_OK;
     DevCtx* ctx = nullptr;
-    int rc = current_ctx(&ctx);
-    if (rc) return rc;
+    int rc = batch_begin(
+        "qfec_verify", bad_batch(code, groups, block_size, pitch) || (groups > 0 && (!d_data || (code->m > 0 && !d_parity))),
+        [&] {
+            if (code->m <= 32) return QFEC_OK;
+            set_error("qfec_verify: m = %d > 32 (one bit per parity row in a 32-bit word)", code->m);
+            return QFEC_EUNSUP;
+        },
+        groups == 0 || (!d_bad_rows && !d_bad_groups), &ctx);
+    if (rc || !ctx) return rc;
     hipStream_t s = (hipStream_t)stream;
     // the per-group words also decide which OR counts a group, so a call that only wants the
     // counter gets them from stream-ordered scratch
-    unsigned* rows = d_bad_rows;
-    if (!rows && hipMallocAsync((void**)&rows, (size_t)groups * 4, s) != hipSuccess)
-        return hip_fail(hipGetLastError(), "verify scratch");
-    auto done = [&](int r) {
-        if (!d_bad_rows) (void)hipFreeAsync(rows, s);
-        return r;
-    };
-    hipError_t he = hipMemsetAsync(rows, 0, (size_t)groups * 4, s);
-    if (he != hipSuccess) return done(hip_fail(he, "verify: zeroing bad_rows"));
-    if (code->m == 0) return done(QFEC_OK);
+    GroupWords words(s);
+    rc = words.init("verify", groups, 1, d_bad_rows);
+    if (rc || code->m == 0) return rc;
     uint32_t* tab = nullptr;
     {
         std::lock_guard<std::mutex> lk(code->mu);
         rc = ensure_enc(code, ctx->device, &tab);
     }
-    if (rc) return done(rc);
+    if (rc) return rc;
     VerifyArgs a{};
     a.tab = tab;
     a.bad_groups = d_bad_groups;
@@ -189,21 +163,18 @@ int qfec_verify(qfec_code* code, const unsigned char* d_data, const unsigned cha
     a.block = (uint32_t)block_size;
     a.dgs = (uint64_t)code->k * pitch;
     a.pgs = (uint64_t)code->m * pitch;
-    a.vec16 = vec16_ok(d_data, d_parity, block_size, pitch) ? 1 : 0;
-    a.cols = a.vec16 ? (uint32_t)((block_size + 15) / 16) : (uint32_t)block_size;
-    a.cols_div = make_div_magic(a.cols);
-    // batches of >= 2^31 lanes go in several launches, as the encode's (run_encode)
-    const long long per = std::max<long long>(1, (long long)(0x7FFFFFFFll / a.cols));
-    for (long long g0 = 0; g0 < groups; g0 += per) {
-        const long long gn = std::min(per, groups - g0);
+    const FlatGeom f = flat_geom(d_data, d_parity, block_size, pitch, a.dgs, a.pgs);
+    a.vec16 = f.vec16;
+    a.cols = f.cols;
+    a.cols_div = make_div_magic(f.cols);
+    return for_group_chunks(groups, f.per, [&](long long g0, long long gn) {
         a.data = d_data + (size_t)g0 * a.dgs;
         a.parity = d_parity + (size_t)g0 * a.pgs;
-        a.bad_rows = rows + g0;
+        a.bad_rows = words.at(0) + g0;
         a.work = (uint64_t)gn * a.cols;
-        he = launch_verify(a, s);
-        if (he != hipSuccess) return done(hip_fail(he, "verify kernel launch"));
-    }
-    return done(QFEC_OK);
+        const hipError_t he = launch_verify(a, s);
+        return he == hipSuccess ? QFEC_OK : hip_fail(he, "verify kernel launch");
+    });
 }
 
 }  // extern "C"

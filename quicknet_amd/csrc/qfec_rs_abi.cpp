@@ -541,7 +541,7 @@ int rs_reconstruct_pipe(DevCtx& ctx, qfec_code* c, const uint8_t* seed, unsigned
             const hipError_t e = hipMemcpyAsync(dd, h.h_in, used, hipMemcpyHostToDevice, h.stream);
             if (e != hipSuccess) { rc = hip_fail(e, "reed_solomon_reconstruct: H2D"); break; }
         }
-        if ((rc = run_reconstruct(*L.ctx, c, L.d->d_lut, nullptr, L.d->d_rec, dd, dd + (size_t)gn * dg,
+        if ((rc = run_reconstruct(*L.ctx, c, L.d->dec.lut, nullptr, L.d->dec.rec, dd, dd + (size_t)gn * dg,
                                   dd + (size_t)gn * (dg + pg), gn, B, (long long)pitch, nullptr, h.stream)))
             break;
         if (!z) {

@@ -8,8 +8,10 @@
 //   qfec_pipe.cpp      qfec_pipe_* (host batches streamed over several streams and devices)
 //   qfec_wire_api.cpp  the datagram / framing entry points (qfec_pack_*, qfec_unpack_*, ...)
 //   qfec_repair.cpp    qfec_repair (its LUT and records) and qfec_verify
-//   qfec_locate.cpp    qfec_locate (its ratio tables), qfec_scrub
+//   qfec_locate.cpp    qfec_locate (its ratio tables), qfec_scrub, and what the locate family shares:
+//                      the code check, the ratio formula, the scrub driver
 //   qfec_locate_erased.cpp  qfec_locate_erased (its LUT and records), qfec_scrub_erased
+// Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,6 +35,7 @@
 #include "../../include/qfec.h"
 #include "../../include/qfec_fec.h"
 #include "../../include/qfec_rs.h"
+#include "qfec_geom.hpp"
 #include "qfec_internal.hpp"
 #include "qfec_maps.hpp"
 #include "qfec_percall.hpp"
@@ -139,6 +142,42 @@ int gather_rows(DevCtx& c, unsigned char* const* ptrs, size_t count, int len, si
 int scatter_rows(DevCtx& c, unsigned char* const* ptrs, size_t count, int len, size_t pitch, const uint8_t* d_src,
                  uint8_t* h_tmp, bool dev_dst, const uint8_t* only);
 
+// Per-group working words of one call, from stream-ordered scratch: `arrays` x [groups] unsigned,
+// array 0 preset to zero, array 1 to all ones.  Freed on the stream when the object goes.  A call
+// that needs one array may bring its own (`given`), which is then preset and not freed.
+class GroupWords {
+public:
+    explicit GroupWords(hipStream_t s) : s_(s) {}
+    ~GroupWords() {
+        if (own_) (void)hipFreeAsync(own_, s_);
+    }
+    GroupWords(const GroupWords&) = delete;
+    GroupWords& operator=(const GroupWords&) = delete;
+    int init(const char* who, long long groups, int arrays, unsigned* given = nullptr);
+    unsigned* at(int i) const { return w_ + (size_t)i * groups_; }
+
+private:
+    hipStream_t s_;
+    unsigned *own_ = nullptr, *w_ = nullptr;
+    size_t groups_ = 0;
+};
+
+// The head of a batched entry point: refuses bad arguments under the entry's name, asks the entry's
+// own check of the code, and fetches the calling thread's device context.  *ctx stays null when
+// there is nothing to do (`empty`) or the call is refused.
+inline bool bad_batch(const qfec_code* code, long long groups, int block_size, long long pitch) {
+    return !code || groups < 0 || block_size < 1 || pitch < block_size;
+}
+template <class Check>
+int batch_begin(const char* who, bool bad_args, Check&& code_check, bool empty, DevCtx** ctx) {
+    if (bad_args) {
+        set_error("%s: invalid argument", who);
+        return QFEC_EINVAL;
+    }
+    const int rc = code_check();
+    return rc || empty ? rc : current_ctx(ctx);
+}
+
 // ---- the resident per-call server (qfec_fec_abi.cpp)
 bool pc_server_alive(const DevCtx::PcServer& s);
 hipError_t pc_server_stop(DevCtx& c, long long limit_us = -1);  // limit_us >= 0: bounded wait
@@ -146,20 +185,21 @@ hipError_t pc_server_stop(DevCtx& c, long long limit_us = -1);  // limit_us >= 0
 }  // namespace qfec
 
 // ---- code objects (qfec_runtime.cpp); qfec_code is the C ABI's opaque type
+// a pattern LUT on one device: [2^n] mask -> record offset (dwords) or a negative code, and the records
+struct DevLut {
+    int32_t* lut = nullptr;
+    uint32_t* rec = nullptr;
+    uint64_t version = ~0ull;  // the code->version it was built from
+};
+
 struct DevTables {
     uint32_t* d_enc = nullptr;  // [m][k][8]
     uint64_t enc_version = ~0ull;
-    int32_t* d_lut = nullptr;    // [2^n]
-    uint32_t* d_rec = nullptr;   // decode records
-    uint64_t rec_version = ~0ull;
-    int32_t* d_rep_lut = nullptr;   // [2^n] repair: full n-bit mask -> compact record (qfec_repair.cpp)
-    uint32_t* d_rep_rec = nullptr;  // compact repair records
-    uint64_t rep_version = ~0ull;
-    uint32_t* d_loc = nullptr;      // [k][m-1][8] locate: perm tables of P[j][i] / P[0][i] (qfec_locate.cpp)
+    DevLut dec;                 // reconstruct: decode records, shared between masks that differ in unused parity
+    DevLut rep;                 // repair: full n-bit mask -> compact record (qfec_repair.cpp)
+    uint32_t* d_loc = nullptr;  // [k][m-1][8] locate: perm tables of P[j][i] / P[0][i] (qfec_locate.cpp)
     uint64_t loc_version = ~0ull;
-    int32_t* d_le_lut = nullptr;    // [2^n] locate-erased: full n-bit mask -> record (qfec_locate_erased.cpp)
-    uint32_t* d_le_rec = nullptr;   // LocErasedLayout records
-    uint64_t le_version = ~0ull;
+    DevLut le;                  // locate-erased: full n-bit mask -> LocErasedLayout record (qfec_locate_erased.cpp)
 };
 
 struct qfec_code {
@@ -193,7 +233,8 @@ void free_code(qfec_code* c);
 const uint8_t* full_of(const qfec_code* c);  // module/rs.c's rs->m, or nullptr
 int ensure_enc(qfec_code* c, int dev, uint32_t** out);    // caller holds c->mu
 int ensure_lut(qfec_code* c, int dev, DevTables** out);   // caller holds c->mu
-bool vec16_ok(const void* a, const void* b, int block, long long pitch);
+// replaces d's tables by (lut, recs) and stamps the version (synchronous; caller holds c->mu)
+int upload_lut(DevLut& d, const std::vector<int32_t>& lut, const std::vector<uint32_t>& recs, uint64_t version);
 int run_encode(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, int m, const uint8_t* d_data, uint8_t* d_par,
                long long groups, int block, long long pitch, hipStream_t s, long long dgs = -1, long long pgs = -1,
                bool host_mem = false);
@@ -206,5 +247,17 @@ int host_records(qfec_code* c, const uint8_t* marks, long long groups, std::vect
 int reconstruct_host_records(DevCtx& ctx, qfec_code* c, uint8_t* d_data, const uint8_t* d_par,
                              const uint8_t* d_marks, long long groups, int block_size, long long pitch,
                              unsigned* d_failed, hipStream_t s);
+
+// ---- shared by the locate family (qfec_locate.cpp)
+// Can single-shard location work on this code at all?  Decided on the host, before any device.
+// need_lut: also the width of a LUT keyed by the whole mask.
+int locate_code_check(const qfec_code* c, const char* who, bool need_lut);
+// out[i * (S - 1) + (x - 1)] = rows[x][i] / rows[0][i], x = 1..S-1 (0 where rows[0][i] is 0); rows is S x k
+void ratio_rows(const uint8_t* rows, int S, int k, std::vector<uint8_t>& out);
+// locate(marks, extra), then qfec_repair with the marks it wrote; both from stream-ordered scratch
+// (`extra` bytes follow the marks)
+int run_scrub(const char* who, qfec_code* code, uint8_t* d_data, uint8_t* d_parity, long long groups, int block_size,
+              long long pitch, size_t extra, unsigned* d_failed, hipStream_t s,
+              const std::function<int(uint8_t* marks, uint8_t* extra)>& locate);
 
 }  // namespace qfec

@@ -296,13 +296,11 @@ void free_code(qfec_code* c) {
     for (auto& kv : c->dev) {
         if (hipSetDevice(kv.first) != hipSuccess) continue;
         if (kv.second.d_enc) (void)hipFree(kv.second.d_enc);
-        if (kv.second.d_lut) (void)hipFree(kv.second.d_lut);
-        if (kv.second.d_rec) (void)hipFree(kv.second.d_rec);
-        if (kv.second.d_rep_lut) (void)hipFree(kv.second.d_rep_lut);
-        if (kv.second.d_rep_rec) (void)hipFree(kv.second.d_rep_rec);
         if (kv.second.d_loc) (void)hipFree(kv.second.d_loc);
-        if (kv.second.d_le_lut) (void)hipFree(kv.second.d_le_lut);
-        if (kv.second.d_le_rec) (void)hipFree(kv.second.d_le_rec);
+        for (DevLut* l : {&kv.second.dec, &kv.second.rep, &kv.second.le}) {
+            if (l->lut) (void)hipFree(l->lut);
+            if (l->rec) (void)hipFree(l->rec);
+        }
     }
     if (have) (void)hipSetDevice(prev);
     delete c;
@@ -376,7 +374,7 @@ int record_for_key(const qfec_code* c, uint64_t key, std::vector<uint32_t>& rec)
 int ensure_lut(qfec_code* c, int dev, DevTables** out) {
     DevTables& d = c->dev[dev];
     *out = &d;
-    if (d.rec_version == c->version && d.d_lut) return QFEC_OK;
+    if (d.dec.version == c->version && d.dec.lut) return QFEC_OK;
     const int k = c->k, m = c->m, n = k + m;
     if (n > QFEC_LUT_MAX_N) {
         set_error("qfec_reconstruct: k + m = %d > %d (use reed_solomon_reconstruct)", n, QFEC_LUT_MAX_N);
@@ -406,23 +404,39 @@ int ensure_lut(qfec_code* c, int dev, DevTables** out) {
         off_of.emplace(key, off);
         lut[mask] = off;
     }
-    if (d.d_lut) HIP_TRY(hipFree(d.d_lut));
-    if (d.d_rec) HIP_TRY(hipFree(d.d_rec));
-    d.d_lut = nullptr;
-    d.d_rec = nullptr;
-    HIP_TRY(hipMalloc(&d.d_lut, nmask * 4));
-    HIP_TRY(hipMalloc(&d.d_rec, std::max<size_t>(recs.size(), 8) * 4));
-    HIP_TRY(hipMemcpy(d.d_lut, lut.data(), nmask * 4, hipMemcpyHostToDevice));
-    if (!recs.empty()) HIP_TRY(hipMemcpy(d.d_rec, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
-    d.rec_version = c->version;
+    const int rc = upload_lut(d.dec, lut, recs, c->version);
+    if (rc) return rc;
     c->lut_seed = std::make_shared<const std::vector<uint8_t>>(std::move(seed));
     c->lut_seed_version = c->version;
     return QFEC_OK;
 }
 
-bool vec16_ok(const void* a, const void* b, int block, long long pitch) {
-    return ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) && (pitch % 16 == 0) &&
-           (long long)round_up((size_t)block, 16) <= pitch;
+int upload_lut(DevLut& d, const std::vector<int32_t>& lut, const std::vector<uint32_t>& recs, uint64_t version) {
+    if (d.lut) HIP_TRY(hipFree(d.lut));
+    if (d.rec) HIP_TRY(hipFree(d.rec));
+    d.lut = nullptr;
+    d.rec = nullptr;
+    HIP_TRY(hipMalloc(&d.lut, lut.size() * 4));
+    HIP_TRY(hipMalloc(&d.rec, std::max<size_t>(recs.size(), 8) * 4));
+    HIP_TRY(hipMemcpy(d.lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
+    if (!recs.empty()) HIP_TRY(hipMemcpy(d.rec, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
+    d.version = version;
+    return QFEC_OK;
+}
+
+int GroupWords::init(const char* who, long long groups, int arrays, unsigned* given) {
+    groups_ = (size_t)groups;
+    w_ = given;
+    if (!w_) {
+        if (hipMallocAsync((void**)&own_, groups_ * 4 * arrays, s_) != hipSuccess)
+            return hip_fail(hipGetLastError(), (std::string(who) + " scratch").c_str());
+        w_ = own_;
+    }
+    hipError_t he = hipMemsetAsync(w_, 0, groups_ * 4, s_);
+    if (he == hipSuccess && arrays > 1) he = hipMemsetAsync(at(1), 0xFF, groups_ * 4, s_);
+    if (he != hipSuccess)
+        return hip_fail(he, (std::string(who) + (arrays > 1 ? ": presetting the group words" : ": zeroing bad_rows")).c_str());
+    return QFEC_OK;
 }
 
 // launch encode over `groups` groups with tables `tab` covering `m` rows
@@ -436,31 +450,24 @@ int run_encode(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, int m, cons
     a.k = c->k;
     a.m = m;
     a.pitch = (uint64_t)pitch;
-    a.vec16 = vec16_ok(d_data, d_par, block, pitch) ? 1 : 0;
     a.impl = tuning().encode_impl;
     // a cap on resident waves (and the one-wave blocks held to 10 per CU) pays in HBM
     // (qfec_kernels.hip launch_encode), not over PCIe, where latency wants every wave the registers allow
     a.lds = host_mem ? 0 : tuning().encode_lds.load();
     a.block = host_mem ? 256 : tuning().encode_block.load();
-    a.cols = a.vec16 ? (uint32_t)((block + 15) / 16) : (uint32_t)block;
-    a.cols_div = make_div_magic(a.cols);
     a.dgs = dgs >= 0 ? (uint64_t)dgs : (uint64_t)c->k * pitch;
     a.pgs = pgs >= 0 ? (uint64_t)pgs : (uint64_t)m * pitch;
-    if (a.vec16 && ((a.dgs | a.pgs) & 15)) {
-        a.vec16 = 0;
-        a.cols = (uint32_t)block;
-        a.cols_div = make_div_magic(a.cols);
-    }
-    const long long per = std::max<long long>(1, (long long)(0x7FFFFFFFll / a.cols));
-    for (long long g0 = 0; g0 < groups; g0 += per) {
-        const long long gn = std::min(per, groups - g0);
+    const FlatGeom f = flat_geom(d_data, d_par, block, pitch, a.dgs, a.pgs);
+    a.vec16 = f.vec16;
+    a.cols = f.cols;
+    a.cols_div = make_div_magic(f.cols);
+    return for_group_chunks(groups, f.per, [&](long long g0, long long gn) {
         a.data = d_data + (size_t)g0 * a.dgs;
         a.parity = d_par + (size_t)g0 * a.pgs;
         a.work = (uint64_t)gn * a.cols;
-        hipError_t e = launch_encode(a, g_variant.load(), s);
-        if (e != hipSuccess) return hip_fail(e, "encode kernel launch");
-    }
-    return QFEC_OK;
+        const hipError_t e = launch_encode(a, g_variant.load(), s);
+        return e == hipSuccess ? QFEC_OK : hip_fail(e, "encode kernel launch");
+    });
 }
 
 int run_reconstruct(DevCtx& ctx, const qfec_code* c, const int32_t* lut, const int32_t* group_rec,
@@ -487,23 +494,16 @@ int run_reconstruct(DevCtx& ctx, const qfec_code* c, const int32_t* lut, const i
     a.t256 = ctx.d_t256;
     a.dgs = dgs >= 0 ? (uint64_t)dgs : (uint64_t)c->k * pitch;
     a.pgs = pgs >= 0 ? (uint64_t)pgs : (uint64_t)c->m * pitch;
-    a.vec16 = vec16_ok(d_data, d_par, block, pitch) && !((a.dgs | a.pgs) & 15) ? 1 : 0;
-    a.cols = a.vec16 ? (uint32_t)((block + 15) / 16) : (uint32_t)block;
+    const FlatGeom f = flat_geom(d_data, d_par, block, pitch, a.dgs, a.pgs);
+    const Lane8Geom l8 = lane8_geom(f, c->k, block);
+    a.vec16 = f.vec16;
+    a.cols = f.cols;
     a.impl = tuning().recon_impl;
     a.wpg = (a.cols + 63) / 64;
-    a.cols8 = (uint32_t)((block + 7) / 8);
+    a.cols8 = l8.cols8;
+    a.wpg8 = l8.wpg8;
     a.cols12 = (uint32_t)((block + 11) / 12);
-    if (a.vec16 && c->k < 14) {
-        // cover the 16-B columns' span, which the 16-B body writes anyway (it stays inside
-        // the pitch): a row that ends part-way into a 64-B line costs a partial-line write
-        // (B = 1400: 175 -> 176 8-B columns, rows end on 1408 = 22 lines).  It also reads the
-        // extra 8 B of every survivor, and with k = 16 survivors per row written that costs
-        // more than it saves: RS(16,4) B=1400 5 404 GB/s full against 5 508 partial, RS(10,3)
-        // B=1024 6 009 against 5 949 (interleaved A/B, profiles/r03_recon/r03k_ab.txt)
-        a.cols8 = 2u * a.cols;
-        a.cols12 = std::max(a.cols12, a.cols * 16u / 12u);
-    }
-    a.wpg8 = (a.cols8 + 63) / 64;
+    if (a.vec16 && c->k < 14) a.cols12 = std::max(a.cols12, a.cols * 16u / 12u);  // the span lane8_geom covers
     a.wpg12 = (a.cols12 + 63) / 64;
     hipError_t e = launch_reconstruct(a, s);
     if (e != hipSuccess) return hip_fail(e, "reconstruct kernel launch");
@@ -940,7 +940,7 @@ int qfec_reconstruct_host(qfec_code* code, unsigned char* h_data, const unsigned
         memcpy(h.h_in, h_marks, mbytes);
         memset(h.h_in + zc_cnt, 0, 16);
         HIP_TRY(hipMemcpyAsync(h.d_buf, h.h_in, zc_cnt + 16, hipMemcpyHostToDevice, h.stream));
-        rc = run_reconstruct(*ctx, code, d->d_lut, nullptr, d->d_rec, z_data, z_par, h.d_buf, groups, block_size, pitch,
+        rc = run_reconstruct(*ctx, code, d->dec.lut, nullptr, d->dec.rec, z_data, z_par, h.d_buf, groups, block_size, pitch,
                              reinterpret_cast<unsigned*>(h.d_buf + zc_cnt), h.stream);
         if (!rc) {
             const hipError_t e1 = hipMemcpyAsync(h.h_out, h.d_buf + zc_cnt, 16, hipMemcpyDeviceToHost, h.stream);
@@ -983,7 +983,7 @@ int qfec_reconstruct_host(qfec_code* code, unsigned char* h_data, const unsigned
         uint8_t* dd = h.d_buf;
         HIP_TRY(hipMemcpyAsync(dd, h.h_in, used, hipMemcpyHostToDevice, h.stream));
         HIP_TRY(hipMemcpyAsync(dd + cnt_off, h.h_in + cnt_off, 16, hipMemcpyHostToDevice, h.stream));
-        if ((r = run_reconstruct(*ctx, code, d->d_lut, nullptr, d->d_rec, dd, dd + (size_t)gn * dg,
+        if ((r = run_reconstruct(*ctx, code, d->dec.lut, nullptr, d->dec.rec, dd, dd + (size_t)gn * dg,
                                  dd + (size_t)gn * (dg + pg), gn, block_size, pitch,
                                  reinterpret_cast<unsigned*>(dd + cnt_off), h.stream)))
             return r;
@@ -1039,7 +1039,7 @@ int qfec_reconstruct(qfec_code* code, unsigned char* d_data, const unsigned char
         rc = ensure_lut(code, ctx->device, &d);
     }
     if (rc) return rc;
-    return run_reconstruct(*ctx, code, d->d_lut, nullptr, d->d_rec, d_data, d_parity, d_marks, groups, block_size,
+    return run_reconstruct(*ctx, code, d->dec.lut, nullptr, d->dec.rec, d_data, d_parity, d_marks, groups, block_size,
                            pitch, d_failed, (hipStream_t)stream);
 }
 
@@ -1113,9 +1113,11 @@ int qfec_probe_reconstruct(unsigned char* d_data, const unsigned char* d_parity,
     a.m = m;
     a.dgs = (uint64_t)k * pitch;
     a.pgs = (uint64_t)m * pitch;
-    a.cols = (uint32_t)((block_size + 15) / 16);
-    a.cols8 = k < 14 ? 2u * a.cols : (uint32_t)((block_size + 7) / 8);  // as run_reconstruct sets them
-    a.wpg8 = (a.cols8 + 63) / 64;
+    const FlatGeom f = flat_geom(d_data, d_parity, block_size, pitch, a.dgs, a.pgs);  // vec16: checked above
+    const Lane8Geom l8 = lane8_geom(f, k, block_size);
+    a.cols = f.cols;
+    a.cols8 = l8.cols8;
+    a.wpg8 = l8.wpg8;
     a.rlds = lds_cap;
     hipError_t e = launch_probe_recon(a, (hipStream_t)stream);
     return e == hipSuccess ? QFEC_OK : hip_fail(e, "reconstruct probe launch");

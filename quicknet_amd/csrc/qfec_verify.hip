@@ -22,33 +22,12 @@
 
 namespace qfec {
 
-// head_bytes, column_mask and differs (the tail-byte mask and the compare under it) are in
-// qfec_device.hpp, shared with qfec_locate.hip.
+// The product bodies, the tail-byte mask and the compare under it, and the report (flat_report) are
+// in qfec_device.hpp, shared with qfec_locate.hip.
 
-// bad = this lane's row bits for group g (0 for idle lanes).  Every lane of the wave calls it.
-__device__ __forceinline__ void verify_report(const VerifyArgs& a, uint32_t g, uint32_t bad) {
-    uint64_t pending = __ballot(bad != 0);
-    const int lane = threadIdx.x & 63;
-    while (pending) {  // wave-uniform; one round per group with a mismatch in this wave
-        const int leader = __builtin_ctzll(pending);
-        const uint32_t gl = (uint32_t)__shfl((int)g, leader);
-        const bool same = bad != 0 && g == gl;
-        uint32_t rows = 0;
-        for (int j = 0; j < a.m; ++j)
-            if (__ballot(same && ((bad >> j) & 1u))) rows |= 1u << j;
-        if (lane == leader) {
-            const unsigned old = atomicOr(a.bad_rows + gl, rows);
-            if (old == 0 && a.bad_groups) atomicAdd(a.bad_groups, 1u);
-        }
-        pending &= ~__ballot(same);
-    }
-}
-
-// compile-time K, M.  For K >= 16 the inputs come in two halves, as in k_encode_perm_halves: half
-// the input registers live at a time.
+// compile-time K, M
 template <int K, int M>
 __global__ void __launch_bounds__(256) k_verify_perm(VerifyArgs a) {
-    constexpr int H = K >= 16 ? (K + 1) / 2 : K;
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     uint32_t g32 = 0, bad = 0;
     if (t < a.work) {
@@ -56,50 +35,22 @@ __global__ void __launch_bounds__(256) k_verify_perm(VerifyArgs a) {
         const uint32_t col = (uint32_t)(t - g * (uint64_t)a.cols);
         const uint8_t* src = a.data + g * a.dgs + (uint64_t)col * 16u;
         const uint8_t* par = a.parity + g * a.pgs + (uint64_t)col * 16u;
-        const uint32_t* __restrict__ tab = a.tab;
-        uint4 p[M];
+        uint4 p[M], acc[M];
 #pragma unroll
         for (int r = 0; r < M; ++r) p[r] = ld16(par + (uint64_t)r * a.pitch);
-        uint4 acc[M];
 #pragma unroll
         for (int r = 0; r < M; ++r) acc[r] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int c0 = 0; c0 < K; c0 += H) {
-            if (H < K) __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
-            constexpr int HH = H;
-            const int n = min(HH, K - c0);
-            uint4 x[H];
-#pragma unroll
-            for (int i = 0; i < H; ++i)
-                if (i < n) x[i] = ld16(src + (uint64_t)(c0 + i) * a.pitch);
-#pragma unroll
-            for (int i = 0; i + 1 < H; i += 2) {
-                if (i + 1 >= n) continue;
-                Sel sa[4], sb[4];
-                sel16(sa, x[i]);
-                sel16(sb, x[i + 1]);
-#pragma unroll
-                for (int r = 0; r < M; ++r)
-                    gf_mac16x2(acc[r], sa, sb, tab + (r * K + c0 + i) * QFEC_TAB_STRIDE,
-                               tab + (r * K + c0 + i + 1) * QFEC_TAB_STRIDE);
-            }
-            if (n & 1) {
-                Sel sl[4];
-                sel16(sl, x[n - 1]);
-#pragma unroll
-                for (int r = 0; r < M; ++r) gf_mac16(acc[r], sl, tab + (r * K + c0 + n - 1) * QFEC_TAB_STRIDE);
-            }
-        }
+        products16<K, M>(acc, src, a.pitch, a.tab);
         const uint4 mk = column_mask(a.block, col);
 #pragma unroll
         for (int r = 0; r < M; ++r)
             if (differs(acc[r], p[r], mk)) bad |= 1u << r;
         g32 = (uint32_t)g;
     }
-    verify_report(a, g32, bad);
+    flat_report<false>(a.bad_rows, nullptr, a.bad_groups, a.k, a.m, g32, bad, 0);
 }
 
-// runtime k, m (m <= 32): rows in chunks of VCH, the k inputs re-read per chunk (cache hits)
+// runtime k, m (m <= 32): rows in chunks of VCH
 constexpr int VCH = 4;
 
 __global__ void __launch_bounds__(256) k_verify_any(VerifyArgs a) {
@@ -114,23 +65,14 @@ __global__ void __launch_bounds__(256) k_verify_any(VerifyArgs a) {
         const uint4 mk = column_mask(a.block, col);
         for (int r0 = 0; r0 < m; r0 += VCH) {
             uint4 acc[VCH];
-#pragma unroll
-            for (int j = 0; j < VCH; ++j) acc[j] = make_uint4(0, 0, 0, 0);
-            for (int c = 0; c < k; ++c) {
-                const uint4 v = ld16(src + (uint64_t)c * a.pitch);
-                Sel s[4];
-                sel16(s, v);
-#pragma unroll
-                for (int j = 0; j < VCH; ++j)
-                    if (r0 + j < m) gf_mac16(acc[j], s, a.tab + ((r0 + j) * k + c) * QFEC_TAB_STRIDE);
-            }
+            products16_rows<VCH>(acc, src, a.pitch, a.tab, k, m, r0);
 #pragma unroll
             for (int j = 0; j < VCH; ++j)
                 if (r0 + j < m && differs(acc[j], ld16(par + (uint64_t)(r0 + j) * a.pitch), mk)) bad |= 1u << (r0 + j);
         }
         g32 = (uint32_t)g;
     }
-    verify_report(a, g32, bad);
+    flat_report<false>(a.bad_rows, nullptr, a.bad_groups, a.k, a.m, g32, bad, 0);
 }
 
 // byte-granular fallback for pitches / pointers that are not 16-B aligned: one lane per byte of
@@ -144,19 +86,11 @@ __global__ void __launch_bounds__(256) k_verify_bytes(VerifyArgs a) {
         const int k = a.k, m = a.m;
         const uint8_t* src = a.data + g * a.dgs + b;
         const uint8_t* par = a.parity + g * a.pgs + b;
-        for (int r = 0; r < m; ++r) {
-            const uint32_t* tr = a.tab + (r * k) * QFEC_TAB_STRIDE;
-            uint32_t acc = 0;
-            for (int c = 0; c < k; ++c) {
-                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
-                const Sel s = gf_sel((uint32_t)src[(uint64_t)c * a.pitch]);
-                acc ^= gf_mul4(s, tc[0], tc[1], tc[2], tc[3], tc[4]);
-            }
-            if ((uint8_t)acc != par[(uint64_t)r * a.pitch]) bad |= 1u << r;
-        }
+        for (int r = 0; r < m; ++r)
+            if ((uint8_t)product_byte(src, a.pitch, a.tab, k, r) != par[(uint64_t)r * a.pitch]) bad |= 1u << r;
         g32 = (uint32_t)g;
     }
-    verify_report(a, g32, bad);
+    flat_report<false>(a.bad_rows, nullptr, a.bad_groups, a.k, a.m, g32, bad, 0);
 }
 
 #define QFEC_VER_CASE(KK, MM)                                                                    \

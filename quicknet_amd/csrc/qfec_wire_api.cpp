@@ -125,10 +125,10 @@ int qfec_unpack_datagrams(qfec_code* code, const unsigned char* d_wire, long lon
     a.m = m;
     a.checksum = checksum;
     a.dec_pkt_size = dec_pkt_size;
-    if (tuning().wire_rx && d->d_lut) {
+    if (tuning().wire_rx && d->dec.lut) {
         bool launched = false;
         const hipError_t ef =
-            launch_rx(a, d->d_lut, d->d_rec, (uint32_t)record_layout(k, m).hdr, s, &launched);
+            launch_rx(a, d->dec.lut, d->dec.rec, (uint32_t)record_layout(k, m).hdr, s, &launched);
         if (ef != hipSuccess) return hip_fail(ef, "datagram receive launch");
         if (launched) return QFEC_OK;
     }
@@ -136,7 +136,7 @@ int qfec_unpack_datagrams(qfec_code* code, const unsigned char* d_wire, long lon
     if (e != hipSuccess) return hip_fail(e, "parse_wire launch");
     // decode the missing data shards from the first k valid ones in group order
     // (network/NetFecCodec.cpp:504-528 == module/rs.c:620-629)
-    if ((rc = run_reconstruct(*ctx, code, d->d_lut, nullptr, d->d_rec, d_shards, d_shards + (size_t)k * shard_pitch,
+    if ((rc = run_reconstruct(*ctx, code, d->dec.lut, nullptr, d->dec.rec, d_shards, d_shards + (size_t)k * shard_pitch,
                               d_marks, groups, (int)shard_pitch, shard_pitch, nullptr, s, (long long)a.group_stride,
                               (long long)a.group_stride)))
         return rc;
@@ -224,7 +224,7 @@ int qfec_unpack_frames(qfec_code* code, const unsigned char* d_frames, long long
     if (rc) return rc;
     const int k = code->k, m = code->m, n = k + m;
     hipStream_t s = (hipStream_t)stream;
-    if (tuning().wire_rx && d->d_lut) {
+    if (tuning().wire_rx && d->dec.lut) {
         WireArgs a{};
         a.shards = d_shards;
         a.pitch = (uint64_t)shard_pitch;
@@ -243,7 +243,7 @@ int qfec_unpack_frames(qfec_code* code, const unsigned char* d_frames, long long
         a.dec_pkt_size = dec_pkt_size;
         FrameRecv fr{(uint32_t)gmask & 0xFFu, d_frame_status, session ? d_conv_hid : nullptr};
         bool launched = false;
-        const hipError_t e = launch_unpack_frames(a, fr, fp, d->d_lut, d->d_rec, (uint32_t)record_layout(k, m).hdr, s,
+        const hipError_t e = launch_unpack_frames(a, fr, fp, d->dec.lut, d->dec.rec, (uint32_t)record_layout(k, m).hdr, s,
                                                   &launched);
         if (e != hipSuccess) return hip_fail(e, "unpack_frames launch");
         if (launched) return QFEC_OK;

@@ -1,10 +1,13 @@
-"""Shared by test_repair_rows.py, test_gpu_repair.py and test_gpu_verify.py: the expectation of a
-group repair, built from the oracle's reconstruct and encode (nothing new in oracle/)."""
+"""Shared by test_repair_rows.py and the GPU tests of repair, verify, locate and locate_erased: the
+expectation of a group repair, built from the oracle's reconstruct and encode (nothing new in
+oracle/), and the device batches those GPU tests start from.  torch is imported inside the helpers
+that need it, so the CPU tests that import this module need no device."""
+import functools
 import itertools
 
 import numpy as np
 
-from quicknet_amd.synth import marks_to_rs_layout
+from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
 
 
 def round16(x):
@@ -65,3 +68,46 @@ def expected_repair(oracle, code, flavour, data, par, gm, B):
     # a group with t > m is left alone by the oracle's reconstruct too (e > surviving parity)
     assert np.array_equal(exp[~ok], data[~ok])
     return exp, exp_par, int((~ok).sum())
+
+
+def to_dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+@functools.lru_cache(maxsize=None)
+def _encoded(flavour, k, m, B, pitch, G):
+    import torch
+
+    import quicknet_amd as qa
+
+    code = getattr(qa.Code, flavour)(k, m)
+    data = to_dev(synth_bytes(k * 3 + B, G * k * pitch).reshape(G, k, pitch))
+    par = torch.empty((G, m, pitch), dtype=torch.uint8, device=data.device)
+    code.encode(data, par, B)
+    torch.cuda.synchronize()
+    if pitch > B:
+        par[..., B:] = to_dev(synth_bytes(k * 5 + B, G * m * (pitch - B)).reshape(G, m, pitch - B))
+    return code, data, par
+
+
+def encoded(flavour, k, m, B, pitch, G):
+    """A consistent batch: (code, data [G, k, pitch], parity [G, m, pitch]) on the device with random
+    garbage in [B, pitch) of both.  Encoded once per case; every test gets copies of its own."""
+    code, data, par = _encoded(flavour, k, m, B, pitch, G)
+    return code, data.clone(), par.clone()
+
+
+def shard(data, par, g, c):
+    """Row c of group g over all n shards (a view)."""
+    k = data.shape[1]
+    return data[g, c] if c < k else par[g, c - k]
+
+
+def one_hot_marks(culprit, k, n):
+    """rs.c-layout marks with one mark per group whose culprit is a shard id."""
+    gm = np.zeros((len(culprit), n), np.uint8)
+    hit = culprit >= 0
+    gm[np.nonzero(hit)[0], culprit[hit]] = 1
+    return marks_to_rs_layout(gm, k)

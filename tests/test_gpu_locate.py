@@ -5,13 +5,12 @@ the damage was made.
 
 Run on an MI355X:  python -m pytest tests/test_gpu_locate.py -m gpu -q
 """
-import functools
-
 import numpy as np
 import pytest
 
 import quicknet_amd as qa
-from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
+from quicknet_amd.synth import synth_bytes
+from repair_common import encoded, one_hot_marks, shard, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -32,36 +31,6 @@ CASES_M3 = [c for c in CASES if c[2] >= 3]  # distance >= 4: two corrupted shard
 case_params = pytest.mark.parametrize("flavour,k,m,B,pitch,G", CASES)
 
 
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _encoded(flavour, k, m, B, pitch, G):
-    code = getattr(qa.Code, flavour)(k, m)
-    data = to_dev(synth_bytes(k * 3 + B, G * k * pitch).reshape(G, k, pitch))
-    par = torch.empty((G, m, pitch), dtype=torch.uint8, device=DEV)
-    code.encode(data, par, B)
-    torch.cuda.synchronize()
-    if pitch > B:
-        par[..., B:] = to_dev(synth_bytes(k * 5 + B, G * m * (pitch - B)).reshape(G, m, pitch - B))
-    return code, data, par
-
-
-def encoded(flavour, k, m, B, pitch, G):
-    """A consistent batch, built as test_gpu_verify.encoded builds it: (code, data [G, k, pitch],
-    parity [G, m, pitch]) on the device with random garbage in [B, pitch) of both.  Encoded once
-    per case; every test gets copies of its own."""
-    code, data, par = _encoded(flavour, k, m, B, pitch, G)
-    return code, data.clone(), par.clone()
-
-
-def shard(data, par, g, c):
-    """Row c of group g over all n shards (a view)."""
-    k = data.shape[1]
-    return data[g, c] if c < k else par[g, c - k]
-
-
 def locate(code, data, par, B, counts=None, junk=False):
     """-> (culprit [G], marks [G*n], counts [3]) on the host."""
     G, n = data.shape[0], code.k + code.m
@@ -72,13 +41,6 @@ def locate(code, data, par, B, counts=None, junk=False):
     torch.cuda.synchronize()
     assert culprit is None or out is culprit
     return out.cpu().numpy(), marks.cpu().numpy(), counts.cpu().numpy()
-
-
-def one_hot_marks(culprit, k, n):
-    gm = np.zeros((len(culprit), n), np.uint8)
-    hit = culprit >= 0
-    gm[np.nonzero(hit)[0], culprit[hit]] = 1
-    return marks_to_rs_layout(gm, k)
 
 
 @case_params

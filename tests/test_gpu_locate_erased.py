@@ -6,13 +6,12 @@ The rows of lost shards are filled with junk: they are never read.
 
 Run on an MI355X:  python -m pytest tests/test_gpu_locate_erased.py -m gpu -q
 """
-import functools
-
 import numpy as np
 import pytest
 
 import quicknet_amd as qa
 from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
+from repair_common import encoded, shard, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -34,36 +33,6 @@ CASES = [("cauchy", 10, 3, 1024, 1040, 300), ("cauchy", 16, 4, 1400, 1424, 301),
 # so blocks straddle groups and the last block is part empty (41 x 5 = 205 waves)
 WIDE = ("cauchy", 10, 3, 2100, 2112, 41)
 case_params = pytest.mark.parametrize("flavour,k,m,B,pitch,G", CASES + [WIDE])
-
-
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _encoded(flavour, k, m, B, pitch, G):
-    code = getattr(qa.Code, flavour)(k, m)
-    data = to_dev(synth_bytes(k * 3 + B, G * k * pitch).reshape(G, k, pitch))
-    par = torch.empty((G, m, pitch), dtype=torch.uint8, device=DEV)
-    code.encode(data, par, B)
-    torch.cuda.synchronize()
-    if pitch > B:
-        par[..., B:] = to_dev(synth_bytes(k * 5 + B, G * m * (pitch - B)).reshape(G, m, pitch - B))
-    return code, data, par
-
-
-def encoded(flavour, k, m, B, pitch, G):
-    """A consistent batch, built as test_gpu_locate.encoded builds it: (code, data [G, k, pitch],
-    parity [G, m, pitch]) on the device with random garbage in [B, pitch) of both.  Encoded once
-    per case; every test gets copies of its own."""
-    code, data, par = _encoded(flavour, k, m, B, pitch, G)
-    return code, data.clone(), par.clone()
-
-
-def shard(data, par, g, c):
-    """Row c of group g over all n shards (a view)."""
-    k = data.shape[1]
-    return data[g, c] if c < k else par[g, c - k]
 
 
 def damage(row, kind, B, seed):

@@ -9,7 +9,7 @@ import pytest
 
 import quicknet_amd as qa
 from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
-from repair_common import damage, expected_repair, masks_up_to, padded, random_marks, round16
+from repair_common import damage, expected_repair, masks_up_to, padded, random_marks, round16, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +18,6 @@ if not torch.cuda.is_available():
     pytest.skip("no GPU", allow_module_level=True)
 
 DEV = torch.device("cuda:0")
-
-
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def run_repair(oracle, code, flavour, data, par, gm, B, pitch, pad_fill=0xC3):

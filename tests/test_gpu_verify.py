@@ -4,12 +4,15 @@ gains one per inconsistent group and accumulates.
 
 Run on an MI355X:  python -m pytest tests/test_gpu_verify.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
 import quicknet_amd as qa
 from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
-from repair_common import damage, padded, random_marks, round16
+from repair_common import damage, padded, random_marks, round16, to_dev
+from repair_common import encoded as encoded_flavour
 
 pytestmark = pytest.mark.gpu
 
@@ -25,21 +28,7 @@ CASES = [(10, 3, 1024, 1040, 300), (16, 4, 1400, 1424, 300), (9, 5, 100, 128, 30
          (10, 3, 1024, 1040, 301)]
 
 
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def encoded(k, m, B, pitch, G):
-    """A consistent batch: (code, data [G, k, pitch], parity [G, m, pitch]) on the device, with
-    random garbage in [B, pitch) of both."""
-    code = qa.Code.cauchy(k, m)
-    data = to_dev(synth_bytes(k * 3 + B, G * k * pitch).reshape(G, k, pitch))
-    par = torch.empty((G, m, pitch), dtype=torch.uint8, device=DEV)
-    code.encode(data, par, B)
-    torch.cuda.synchronize()
-    if pitch > B:
-        par[..., B:] = to_dev(synth_bytes(k * 5 + B, G * m * (pitch - B)).reshape(G, m, pitch - B))
-    return code, data, par
+encoded = functools.partial(encoded_flavour, "cauchy")  # (k, m, B, pitch, G) -> code, data, parity
 
 
 def verify(code, data, par, B, count=None):
