@@ -219,6 +219,61 @@ int qfec_scrub(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
  * qfec_repair_rows. */
 int qfec_locate_ratios(const qfec_code *code, unsigned char *out /* k*(m-1): r_{j,i} at [i*(m-1)+(j-1)] */);
 
+/* Which TWO shards are wrong?  qfec_locate stops at one corrupted shard per group and calls the rest
+ * MULTI.  A code with m >= 4 parity rows has minimum distance m + 1 >= 5 and determines two corrupted
+ * shards uniquely.  With H = [rows | I_m], h_x = column x of the parity rows for a data shard x < k
+ * and the unit vector e_j for parity row x = k + j, and the syndromes s of qfec_locate (true GF
+ * products, no rs.c stale-row quirk), a pair {a, b}, a < b, is a candidate iff s lies in
+ * span{h_a, h_b} at EVERY byte of [0, block_size).  d_culprit has two slots per group:
+ *   consistent                               QFEC_LOC_CLEAN, QFEC_LOC_CLEAN
+ *   one corrupted shard                      its id exactly as qfec_locate gives it, QFEC_LOC_CLEAN
+ *   qfec_locate says MULTI, one candidate    a, b
+ *   qfec_locate says MULTI, no candidate     QFEC_LOC_MULTI, QFEC_LOC_MULTI
+ *   qfec_locate says MULTI, several          QFEC_LOC_AMBIGUOUS, QFEC_LOC_AMBIGUOUS
+ * Several candidate pairs can only happen for explicit rows of distance exactly 4, or for three or
+ * more corrupted shards at m = 4.  With m >= 5 (distance >= 6) three corrupted shards are never taken
+ * for two: the verdict is MULTI.  With m = 4 (distance 5) the verdict for three or more corrupted
+ * shards is undefined (a wrong pair is possible), as for m = 2 in qfec_locate.
+ * d_marks (rs.c layout, groups * (k + m) bytes, may be NULL) is written for every group: 1 at each
+ * culprit, 0 everywhere else, ready for qfec_repair.  d_counts ([4], may be NULL; accumulated, not
+ * reset) gains 1 per group with one culprit, with two, per MULTI and per AMBIGUOUS group.  Layouts,
+ * pitch, the 16-byte fast path and the byte path, launch chunking and the stream are qfec_locate's;
+ * bytes in [block_size, pitch) never count and nothing in d_data / d_parity is written.
+ * Asynchronous on `stream`, no host synchronisation and no read-back; the working memory comes from
+ * stream-ordered scratch.  A consistent batch costs qfec_locate's time plus four small launches;
+ * only the groups qfec_locate calls MULTI are read a second time (one wave each, every pair of
+ * shards tested against the recomputed syndromes).
+ * QFEC_EUNSUP, decided on the host before a device is touched, with the cause in qfec_last_error:
+ * everything qfec_locate refuses; m < 4; k + m > 24; some three columns of H linearly dependent (the
+ * code's distance is then below 4, and one and two corrupted shards cannot be told apart).  Codes
+ * from qfec_code_new never hit the last case, and a code that passes it cannot give AMBIGUOUS from
+ * the single-shard stage.  At most 2^32 - 1 groups per call. */
+int qfec_locate2(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                 long long groups, int block_size, long long pitch,
+                 int *d_culprit          /* [groups][2]: shard ids a < b, or QFEC_LOC_* */,
+                 unsigned char *d_marks  /* rs.c layout, groups*(k+m) bytes, nullable */,
+                 unsigned int *d_counts  /* [4] one, two, multi, ambiguous; accumulates; nullable */,
+                 void *stream);
+
+/* qfec_locate2 into stream-ordered scratch marks, then qfec_repair with those marks, in one call:
+ * groups with one or two corrupted shards are back to their original bytes in [0, block_size);
+ * CLEAN, MULTI and AMBIGUOUS groups are untouched byte for byte (the latter two are reported only,
+ * in d_culprit ([groups][2], may be NULL) and d_counts ([4], may be NULL; accumulated)).
+ * Asynchronous on `stream` once the repair LUT exists (qfec_prepare_repair, or the first call).
+ * QFEC_EUNSUP as for qfec_locate2, checked before anything is launched. */
+int qfec_scrub2(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                long long groups, int block_size, long long pitch,
+                int *d_culprit /* [groups][2], nullable */, unsigned int *d_counts /* [4], nullable */,
+                void *stream);
+
+/* The host-built constants of qfec_locate2 for the pair {a, b}: m - 2 rows F (out[r*m + j]) of rank
+ * m - 2 with F x h_a = 0 and F x h_b = 0, the left null space of [h_a h_b] in the basis the device
+ * constants are derived from: with p0 < p1 the first two rows on which [h_a h_b] is invertible, the
+ * row of every other j has 1 at j and the coefficients of s_p0 and s_p1 that predict s_j.  Returns
+ * m - 2.  QFEC_EINVAL for a = b or ids outside 0..k+m-1; QFEC_EUNSUP as for qfec_locate2.  CPU only,
+ * like qfec_locate_ratios. */
+int qfec_locate2_checks(const qfec_code *code, int a, int b, unsigned char *out /* (m-2)*m */);
+
 /* Which SURVIVING shard is wrong, in a group that also has lost shards?  qfec_locate needs all k + m
  * shards of a group; on a lossy link that is the rare case.  A group with t <= m - 2 marked (lost)
  * shards still holds m - t >= 2 shards more than the k a decode needs, and those can name one

@@ -19,6 +19,7 @@ EXPORTS = {
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
+               "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
                "qfec_pipe_new", "qfec_pipe_free", "qfec_pipe_encode", "qfec_pipe_reconstruct", "qfec_pipe_wait", "qfec_pipe_slots",
                "qfec_fec_code", "qfec_rs_code", "qfec_fec_matrix", "qfec_pack_datagrams", "qfec_unpack_datagrams",
@@ -83,6 +84,9 @@ def lib():
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),
+        "qfec_locate2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_scrub2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
+        "qfec_locate2_checks": (i, [vp, i, i, vp]),
         "qfec_locate_erased": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_prepare_locate_erased": (i, [vp]),
         "qfec_scrub_erased": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),

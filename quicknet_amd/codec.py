@@ -301,10 +301,12 @@ class Code:
             return t, None, None, None
         return t, rows[:t].copy(), surv, lost[:t].copy()
 
-    def _group_args(self, what, data, parity, block_size, out, out_name="culprit", counts=None, ncounts=0, marks=None):
-        """The checks verify / locate / scrub and the two erased calls share -> (G, block_size, pitch,
-        out): out is the call's per-group device int32 [G] result, allocated when not given; marks
-        (the erased calls' input) and counts are checked when given."""
+    def _group_args(self, what, data, parity, block_size, out, out_name="culprit", counts=None, ncounts=0, marks=None,
+                    slots=1):
+        """The checks verify / locate / scrub, the two erased calls and the two-shard calls share ->
+        (G, block_size, pitch, out): out is the call's per-group device int32 [G] result ([G, slots]
+        for the two-shard calls), allocated when not given; marks (the erased calls' input) and counts
+        are checked when given."""
         import torch
         G, k, pitch = data.shape
         with_marks = "" if marks is None else f"marks {marks.numel()} "
@@ -313,9 +315,9 @@ class Code:
             raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
                             f"{with_marks}for ({self.k},{self.m})")
         if out is None:
-            out = torch.empty(G, dtype=torch.int32, device=data.device)
-        elif out.numel() != G:
-            raise QfecError(f"{what}: {out_name} has {out.numel()} elements for {G} groups")
+            out = torch.empty(G if slots == 1 else (G, slots), dtype=torch.int32, device=data.device)
+        elif out.numel() != G * slots:
+            raise QfecError(f"{what}: {out_name} has {out.numel()} elements for {G} groups" + (f" of {slots}" if slots > 1 else ""))
         if counts is not None and counts.numel() != ncounts:
             raise QfecError(f"{what}: counts has {counts.numel()} elements, not {ncounts}")
         return G, pitch if block_size is None else block_size, pitch, out
@@ -364,6 +366,42 @@ class Code:
         check(lib().qfec_locate_ratios(self._h, scratch.ctypes.data), "qfec_locate_ratios")
         out[:] = scratch[:out.size].reshape(out.shape)
         return out
+
+    def locate2(self, data, parity, block_size=None, culprit=None, marks=None, counts=None, stream=None):
+        """Which one or two shards of each group are corrupted (qfec_locate2, m >= 4)?  Returns
+        culprit, a device int32 [G, 2] tensor (allocated when not given): (id, CLEAN) for one
+        corrupted shard, (a, b) with a < b for two, else QFEC_LOC_CLEAN / MULTI / AMBIGUOUS in both
+        slots.  marks: optional device uint8 [G*k + G*m] (rs.c layout), written for every group: 1 at
+        each culprit, else 0 -- ready for repair().  counts: optional device int32/uint32 [4]
+        one / two / multi / ambiguous (accumulates)."""
+        G, block_size, pitch, culprit = self._group_args("locate2", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=4, slots=2)
+        if marks is not None and marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"locate2: marks has {marks.numel()} elements for {G} groups of {self.k + self.m}")
+        check(lib().qfec_locate2(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
+                                 pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks, what="marks"),
+                                 _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate2")
+        return culprit
+
+    def scrub2(self, data, parity, block_size=None, culprit=None, counts=None, stream=None):
+        """locate2() + repair() of the located shards in one call (qfec_scrub2): a group with one or
+        two corrupted shards is rewritten to its original bytes, MULTI / AMBIGUOUS groups are left as
+        they are and only reported.  Returns culprit as locate2() does."""
+        G, block_size, pitch, culprit = self._group_args("scrub2", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=4, slots=2)
+        check(lib().qfec_scrub2(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"), G, block_size,
+                                pitch, _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                                _stream_handle(stream)), "qfec_scrub2")
+        return culprit
+
+    def locate2_checks(self, a, b):
+        """The constants of locate2() for the pair {a, b}: uint8 [m-2, m] rows F with F . h_a = 0 and
+        F . h_b = 0, h_x = column x of [rows | I] (CPU only)."""
+        out = np.zeros((max(self.m - 2, 1), max(self.m, 1)), dtype=np.uint8)
+        r = lib().qfec_locate2_checks(self._h, int(a), int(b), out.ctypes.data)
+        if r < 0:
+            check(r, "qfec_locate2_checks")
+        return out[:r].copy()
 
     def prepare_locate_erased(self):
         check(lib().qfec_prepare_locate_erased(self._h), "qfec_prepare_locate_erased")

@@ -145,6 +145,43 @@ struct LocateFinishArgs {
     int k, m;
 };
 
+// two-shard error location (qfec_locate2.hip), after qfec_locate's launches: the groups it called
+// MULTI are listed, and a wave per listed group tests every pair {a, b} of shards: F_ab x s == 0 in
+// every byte, F_ab = the m - 2 rows of the left null space of [h_a h_b] (columns of [rows | I])
+constexpr int QFEC_LOC2_MAX_N = 24;  // C(24, 2) = 276 pair bits in nine 32-bit words
+struct Locate2Args {
+    const uint8_t* data;       // [groups][k][pitch], the whole batch
+    const uint8_t* parity;     // [groups][m][pitch]
+    const uint32_t* tab;       // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    const uint32_t* t256;      // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    const uint32_t* checks;    // [pairs][m-2][m] F_ab[r][j] as the byte offset of its perm table in t256
+                               // (0: a zero entry); pairs in the order (0,1), (0,2), .. (n-2,n-1)
+    const uint32_t* pair_ids;  // [pairs] a | b << 8
+    const int* stage1;         // [groups] qfec_locate's verdicts
+    unsigned int* list;        // [groups] the groups with stage1 == QFEC_LOC_MULTI, in no order
+    unsigned int* list_n;      // how many; zeroed before the list kernel
+    int* verdict2;             // [groups], written for listed groups only: a | b << 8, QFEC_LOC_MULTI
+                               // or QFEC_LOC_AMBIGUOUS
+    uint64_t groups;           // < 2^32
+    uint64_t pitch;
+    uint64_t dgs, pgs;
+    uint32_t cols;             // 16-B columns (vec16) or bytes per row
+    uint32_t block;            // block_size: bytes of a row that count
+    int k, m;                  // 4 <= m, k + m <= QFEC_LOC2_MAX_N
+    int pairs;                 // n (n - 1) / 2
+    int vec16;
+};
+
+struct Locate2FinishArgs {
+    const int* stage1;         // [groups]
+    const int* verdict2;       // [groups], read where stage1 == QFEC_LOC_MULTI
+    int* culprit;              // [groups][2]
+    uint8_t* marks;            // rs.c layout, groups * (k + m) bytes; may be NULL
+    unsigned int* counts;      // [4] one, two, multi, ambiguous; may be NULL
+    uint64_t groups;
+    int k, m;
+};
+
 // single-shard error location in groups that also have lost shards (qfec_locate_erased.hip): the
 // repair body's mapping (a wave sits inside one group); the syndromes are those of the m - t spare
 // parity rows over the k lowest unmarked shards
@@ -277,6 +314,9 @@ hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
 hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
+hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);
+hipError_t launch_locate2_pairs(const Locate2Args& a, hipStream_t stream);
+hipError_t launch_locate2_finish(const Locate2FinishArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased(const LocErasedArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);

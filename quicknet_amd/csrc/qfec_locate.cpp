@@ -59,10 +59,8 @@ static int ensure_loc(qfec_code* c, int dev, uint32_t** out) {
     return QFEC_OK;
 }
 
-// the launches of one qfec_locate: two presets, the main kernel per chunk, the finish kernel
-static int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_parity, long long groups,
-                      int block_size, long long pitch, int* d_culprit, uint8_t* d_marks, unsigned* d_counts,
-                      hipStream_t s) {
+int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_parity, long long groups,
+               int block_size, long long pitch, int* d_culprit, uint8_t* d_marks, unsigned* d_counts, hipStream_t s) {
     uint32_t *tab = nullptr, *rtab = nullptr;
     int rc;
     {

@@ -11,6 +11,7 @@
 //   qfec_locate.cpp    qfec_locate (its ratio tables), qfec_scrub, and what the locate family shares:
 //                      the code check, the ratio formula, the scrub driver
 //   qfec_locate_erased.cpp  qfec_locate_erased (its LUT and records), qfec_scrub_erased
+//   qfec_locate2.cpp   qfec_locate2 (its acceptance check and pair constants), qfec_scrub2
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
@@ -200,6 +201,8 @@ struct DevTables {
     uint32_t* d_loc = nullptr;  // [k][m-1][8] locate: perm tables of P[j][i] / P[0][i] (qfec_locate.cpp)
     uint64_t loc_version = ~0ull;
     DevLut le;                  // locate-erased: full n-bit mask -> LocErasedLayout record (qfec_locate_erased.cpp)
+    uint32_t* d_loc2 = nullptr; // locate2: [pairs][m-2][m] check offsets, then [pairs] ids (qfec_locate2.cpp)
+    uint64_t loc2_version = ~0ull;
 };
 
 struct qfec_code {
@@ -224,6 +227,12 @@ struct qfec_code {
     std::string le_error;
     std::vector<uint32_t> le_recs;
     std::vector<std::pair<uint32_t, int32_t>> le_masks;  // (mask, record offset in dwords)
+    // qfec_locate2's host constants (qfec_locate2.cpp): the checks of every pair, or why the code is
+    // refused; built once per version under mu, uploaded per device
+    uint64_t l2_host_version = ~0ull;
+    int l2_rc = 0;
+    std::string l2_error;
+    std::vector<uint8_t> l2_checks;  // [pairs][m-2][m]: F_ab, pairs in the order (0,1), (0,2), .. (n-2,n-1)
 };
 
 namespace qfec {
@@ -254,6 +263,10 @@ int reconstruct_host_records(DevCtx& ctx, qfec_code* c, uint8_t* d_data, const u
 int locate_code_check(const qfec_code* c, const char* who, bool need_lut);
 // out[i * (S - 1) + (x - 1)] = rows[x][i] / rows[0][i], x = 1..S-1 (0 where rows[0][i] is 0); rows is S x k
 void ratio_rows(const uint8_t* rows, int S, int k, std::vector<uint8_t>& out);
+// the launches of one qfec_locate (validated arguments): two presets, the main kernel per chunk, the
+// finish kernel
+int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_parity, long long groups,
+               int block_size, long long pitch, int* d_culprit, uint8_t* d_marks, unsigned* d_counts, hipStream_t s);
 // locate(marks, extra), then qfec_repair with the marks it wrote; both from stream-ordered scratch
 // (`extra` bytes follow the marks)
 int run_scrub(const char* who, qfec_code* code, uint8_t* d_data, uint8_t* d_parity, long long groups, int block_size,

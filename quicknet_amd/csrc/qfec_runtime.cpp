@@ -297,6 +297,7 @@ void free_code(qfec_code* c) {
         if (hipSetDevice(kv.first) != hipSuccess) continue;
         if (kv.second.d_enc) (void)hipFree(kv.second.d_enc);
         if (kv.second.d_loc) (void)hipFree(kv.second.d_loc);
+        if (kv.second.d_loc2) (void)hipFree(kv.second.d_loc2);
         for (DevLut* l : {&kv.second.dec, &kv.second.rep, &kv.second.le}) {
             if (l->lut) (void)hipFree(l->lut);
             if (l->rec) (void)hipFree(l->rec);
