@@ -169,6 +169,56 @@ int qfec_verify(qfec_code *code, const unsigned char *d_data, const unsigned cha
                 unsigned int *d_bad_rows /* [groups], nullable */,
                 unsigned int *d_bad_groups /* counter, accumulates, nullable */, void *stream);
 
+/* Incremental parity: change part of a group that is already encoded without reading the rest of it.
+ * Both calls rest on linearity, parity_j ^= rows[j][i] x (old_i ^ new_i).  All arithmetic is true
+ * GF(2^8) products from the code's parity rows, as in qfec_verify and qfec_repair: there is no rs.c
+ * stale-row quirk (the encode tables' flag word is ignored), so a zero coefficient contributes
+ * nothing.  Layouts, pitch, stream and the 16-byte fast path against the byte path are exactly
+ * qfec_encode's.  Bytes in [block_size, round_up(block_size, 16)) of a row a call writes are scratch
+ * on the fast path; bytes from round_up(block_size, 16) to pitch, and every row a call does not
+ * address, are never written.  Asynchronous on `stream`: no host synchronisation, no read-back, no
+ * LUT, and no k + m limit (any code qfec_code_new accepts).  d_part / d_rows must not overlap d_parity
+ * or d_data.
+ * QFEC_EINVAL, decided on the host before a device is touched, with the cause in qfec_last_error: a
+ * null code, first < 0, count < 1, first + count > k, groups < 0, block_size < 1, pitch < block_size,
+ * accumulate not 0 or 1, a null buffer with groups > 0 (d_data and d_invalid may be NULL).
+ * groups == 0 or m == 0 returns QFEC_OK and launches nothing.
+ *
+ * qfec_encode_update, the range form, for groups whose data arrives a few shards at a time:
+ *   parity[g][j] (^)= sum_{c < count} rows[j][first + c] x part[g][c]   for every group g and row j
+ * d_part holds only the `count` rows first .. first + count - 1 of every group.  accumulate = 1 XORs
+ * into d_parity, 0 overwrites it.  first = 0, count = k, accumulate = 0 gives qfec_encode's parity for
+ * any code without a quirk-stale coefficient; calling it over any partition of [0, k), the first
+ * piece with accumulate = 0 (or onto zeroed parity) and the others with accumulate = 1, gives the same
+ * parity in bytes [0, block_size).  Reads count (+ m with accumulate) rows per group, writes m. */
+int qfec_encode_update(qfec_code *code, int first, int count,
+                       const unsigned char *d_part   /* [groups][count][pitch] */,
+                       unsigned char *d_parity       /* [groups][m][pitch]     */,
+                       long long groups, int block_size, long long pitch,
+                       int accumulate /* 1: XOR into d_parity, 0: overwrite it */, void *stream);
+
+/* qfec_update, the per-group form, for small writes into stored groups: group g replaces ONE data
+ * shard, i = d_shard[g].
+ *   0 <= i < k   with delta = data[g][i] ^ rows[g] over [0, block_size), every parity row j gets
+ *                parity[g][j] ^= rows[j][i] x delta, and data[g][i] becomes rows[g]: the parity is
+ *                then what a fresh encode of the new data gives.
+ *   i < 0        (QFEC_UPD_NONE) no byte of the group is written, and none of its rows is read.
+ *   i >= k       the group is untouched and counted into *d_invalid (device counter, may be NULL;
+ *                accumulated, not reset).  No table is ever indexed with such an id.
+ * With d_data == NULL, d_rows[g] is the delta itself, computed elsewhere (for example on the node that
+ * holds the data shard), and only the parity is written.  One shard per group per call: several
+ * changed shards of a group are several stream-ordered calls.  A touched group costs 2 + m rows read
+ * and 1 + m written (1 + m and m in delta mode) against the k + m of qfec_encode; an untouched group
+ * costs one 4-byte read. */
+#define QFEC_UPD_NONE (-1)
+int qfec_update(qfec_code *code,
+                const int *d_shard            /* [groups]: data shard id 0..k-1 replaced in group g; < 0 = group untouched */,
+                unsigned char *d_data         /* [groups][k][pitch]; NULL: d_rows holds deltas */,
+                const unsigned char *d_rows   /* [groups][pitch]: the new bytes of shard d_shard[g] (or the delta) */,
+                unsigned char *d_parity       /* [groups][m][pitch] */,
+                long long groups, int block_size, long long pitch,
+                unsigned int *d_invalid       /* counter, accumulates, nullable */, void *stream);
+
 /* Which shard is wrong?  qfec_verify says whether a group's parity matches its data; qfec_locate
  * names the ONE shard, data or parity, whose corruption explains the mismatch, so that it can be
  * marked for qfec_repair.  A code with m >= 2 parity rows has minimum distance m + 1 >= 3 and can

@@ -333,6 +333,36 @@ class Code:
                                 _stream_handle(stream)), "qfec_verify")
         return bad_rows
 
+    def encode_update(self, part, parity, first, block_size=None, accumulate=True, stream=None):
+        """parity[g][j] (^)= sum_c rows[j][first + c] x part[g][c] (qfec_encode_update): part uint8
+        [G, count, pitch] holds the data rows first .. first + count - 1 of every group, parity uint8
+        [G, m, pitch]; accumulate: XOR into parity (True) or overwrite it (False).  True GF products,
+        no rs.c stale-row quirk."""
+        G, count, pitch = part.shape
+        if tuple(parity.shape) != (G, self.m, pitch):
+            raise QfecError(f"shape mismatch: part {tuple(part.shape)} parity {tuple(parity.shape)} for ({self.k},{self.m})")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_encode_update(self._h, int(first), count, _dev_ptr(part, what="part"),
+                                       _dev_ptr(parity, what="parity"), G, block_size, pitch, int(bool(accumulate)),
+                                       _stream_handle(stream)), "qfec_encode_update")
+
+    def update(self, shard, rows, parity, data=None, block_size=None, invalid=None, stream=None):
+        """Replace one data shard per group and bring the parity along (qfec_update).  shard: device
+        int32 [G], the data shard id 0..k-1 group g replaces, QFEC_UPD_NONE (any id < 0) = the group is
+        untouched, an id >= k = untouched and counted; rows uint8 [G, pitch]: the shard's new bytes;
+        parity uint8 [G, m, pitch]; data uint8 [G, k, pitch], or None: rows holds the deltas
+        old ^ new and only the parity is written.  invalid: optional device int32/uint32 [1] counter
+        of groups with an id >= k (accumulates)."""
+        G, pitch = rows.shape
+        if (tuple(parity.shape) != (G, self.m, pitch) or shard.numel() != G
+                or (data is not None and tuple(data.shape) != (G, self.k, pitch))):
+            raise QfecError(f"shape mismatch: shard {shard.numel()} rows {tuple(rows.shape)} parity {tuple(parity.shape)} "
+                            f"data {None if data is None else tuple(data.shape)} for ({self.k},{self.m})")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_update(self._h, _dev_ptr(shard, _I32, "shard"), _dev_ptr(data, what="data"),
+                                _dev_ptr(rows, what="rows"), _dev_ptr(parity, what="parity"), G, block_size, pitch,
+                                _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)), "qfec_update")
+
     def locate(self, data, parity, block_size=None, culprit=None, marks=None, counts=None, stream=None):
         """Which single shard of each group is corrupted (qfec_locate)?  Returns culprit, a device
         int32 [G] tensor (allocated when not given): the shard id 0..k+m-1, or QFEC_LOC_CLEAN (-1),

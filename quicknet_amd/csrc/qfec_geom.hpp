@@ -5,7 +5,8 @@
 // Two mappings exist.  Flat (encode, verify, locate): one lane per 16-byte column, or per byte when
 // the layout is not 16-B aligned, (group, column) flattened over the grid.  8-byte lanes
 // (reconstruct, repair, locate_erased): a wave covers 64 8-byte columns of one group, wpg8 waves
-// per group.  In both no launch has more than 2^31 - 1 lanes; a larger batch goes in several
+// per group.  qfec_update has whole waves per group too, on 16-B columns (WaveGeom); the range form
+// qfec_encode_update is flat.  In all of them no launch has more than 2^31 - 1 lanes; a larger batch goes in several
 // launches over consecutive groups (for_group_chunks).
 #pragma once
 
@@ -56,6 +57,21 @@ inline Lane8Geom lane8_geom(const FlatGeom& f, int k, int block) {
     g.wpg8 = (g.cols8 + 63) / 64;
     g.per = std::max<long long>(1, kMaxLaunchLanes / (64ll * std::max(g.wpg8, 1u)));
     return g;
+}
+
+// qfec_update on 16-B-aligned layouts: the flat mapping's 16-B columns, but whole waves per group
+// (the shard a group replaces, and so its tables, are wave-uniform)
+struct WaveGeom {
+    uint32_t cols, wpg;  // 16-B columns per row, waves per group at 64 of them per wave
+    long long per;       // groups per launch
+};
+
+inline WaveGeom wave_geom(const FlatGeom& f) {
+    WaveGeom w;
+    w.cols = f.cols;
+    w.wpg = (w.cols + 63) / 64;
+    w.per = std::max<long long>(1, kMaxLaunchLanes / (64ll * std::max(w.wpg, 1u)));
+    return w;
 }
 
 // fn(g0, gn) once per launch, over [g0, g0 + gn) ascending; stops at the first non-zero return

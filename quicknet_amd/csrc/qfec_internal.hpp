@@ -114,6 +114,42 @@ struct VerifyArgs {
     int vec16;
 };
 
+// incremental parity, range form (qfec_update.hip): the encode's mapping over `count` of the k columns
+struct EncUpdateArgs {
+    const uint8_t* part;      // [groups][count][pitch]: data rows first .. first + count - 1
+    uint8_t* parity;          // [groups][m][pitch]
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    uint64_t work;            // groups * cols lanes (< 2^31)
+    uint64_t pitch;
+    uint64_t sgs, pgs;        // bytes between groups: part (count * pitch), parity (m * pitch)
+    DivMagic cols_div;
+    uint32_t cols;            // 16-B columns (vec16) or bytes per row
+    int k, m;
+    int first, count;         // 0 <= first, 1 <= count, first + count <= k
+    int accumulate;           // 1: XOR into parity, 0: overwrite it
+    int vec16;
+};
+
+// incremental parity, per-group form (qfec_update.hip): whole waves per group, so the shard id a
+// group names, and with it the m tables of that column, are wave-uniform
+struct UpdateArgs {
+    const int32_t* shard;     // [groups] of this launch: 0..k-1 replaced, < 0 untouched, >= k invalid
+    uint8_t* data;            // [groups][k][pitch], or NULL: rows holds the deltas
+    const uint8_t* rows;      // [groups][pitch]: the new bytes of shard[g], or the delta
+    uint8_t* parity;          // [groups][m][pitch]
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    unsigned int* invalid;    // counter of groups with shard >= k; may be NULL
+    uint64_t groups;
+    uint64_t pitch;
+    uint64_t dgs, pgs;        // bytes between groups: data rows, parity rows (rows: pitch)
+    uint64_t work;            // byte path: groups * cols lanes (< 2^31)
+    DivMagic cols_div;        // byte path
+    uint32_t cols;            // lanes per row: 16-B columns (vec16) or bytes
+    uint32_t wpg;             // vec16: waves per group = ceil(cols / 64)
+    int k, m;
+    int vec16;
+};
+
 // single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
 // syndrome tests every data shard as the culprit
 struct LocateArgs {
@@ -312,6 +348,8 @@ hipError_t launch_encode(const EncodeArgs& a, int variant, hipStream_t stream);
 hipError_t launch_reconstruct(const ReconArgs& a, hipStream_t stream);
 hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
 hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
+hipError_t launch_encode_update(const EncUpdateArgs& a, hipStream_t stream);
+hipError_t launch_update(const UpdateArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);

@@ -12,6 +12,7 @@
 //                      the code check, the ratio formula, the scrub driver
 //   qfec_locate_erased.cpp  qfec_locate_erased (its LUT and records), qfec_scrub_erased
 //   qfec_locate2.cpp   qfec_locate2 (its acceptance check and pair constants), qfec_scrub2
+//   qfec_update.cpp    qfec_encode_update, qfec_update (incremental parity on the encode's tables)
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
