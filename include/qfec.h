@@ -118,6 +118,43 @@ int qfec_reconstruct(qfec_code *code, unsigned char *d_data, const unsigned char
  * (otherwise done on the first qfec_reconstruct). */
 int qfec_prepare_reconstruct(qfec_code *code);
 
+/* qfec_encode and qfec_reconstruct on shards SCATTERED in device memory, for callers that hold one
+ * buffer per packet (module/rs.h's `unsigned char **shards`).  d_shards is a DEVICE array of
+ * groups * (k + m) device pointers in rs.c's shard order (rs.c:578-586, what reed_solomon_encode
+ * receives): the groups * k data shards first, group-major, then the groups * m parity shards.
+ * d_marks is the rs.c marks layout, as for qfec_reconstruct.  Every shard is exactly block_size
+ * bytes: there is no pitch and there are NO scratch bytes -- no byte outside [0, block_size) of any
+ * shard is read or written (the next byte may belong to someone else's packet).
+ *   Encode results: qfec_encode_ptrs writes, into the parity shards, exactly the bytes qfec_encode
+ *     writes for the same rows laid out contiguously: the same tables, the rs.c column-0 stale-row
+ *     quirk included (a flagged row starts from the destination's previous bytes).
+ *   Reconstruct results: qfec_reconstruct_ptrs rewrites the marked data shards exactly as
+ *     qfec_reconstruct does: the same survivor rule, decode records, quirk and *d_failed accounting
+ *     (nullable, accumulated).  Groups with no erased data are untouched; under-determined groups
+ *     are untouched and counted.
+ *   Any alignment: shards may start at any byte, block_size may be any value >= 1.  A group all of
+ *     whose k + m pointers are 16-B aligned runs 16-byte (reconstruct of k >= 10: 8-byte) accesses;
+ *     any other group is worked on byte by byte, much slower.
+ *   Aliasing: shards that are only read may alias each other or repeat (a shared padding shard).  A
+ *     shard the call writes -- the parity in encode, the marked data in reconstruct -- must not
+ *     overlap any other shard of the batch, or the result is undefined.
+ *   Asynchronous on `stream`: no host synchronisation, no read-back.  The pointer table and the
+ *     marks must stay valid until the work has run.
+ *   qfec_reconstruct_ptrs uses the device LUT qfec_reconstruct uses (built on the first call or by
+ *     qfec_prepare_reconstruct).  k + m > 24 returns QFEC_EUNSUP: there is no host-record path
+ *     here.  qfec_encode_ptrs takes any code qfec_code_new accepts.  Batches beyond the 32-bit
+ *     index space of a launch are cut into several launches by the host, as elsewhere.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error: a null code, groups < 0, block_size < 1, a null d_shards with groups > 0, a
+ *     null d_marks with groups > 0.  groups == 0 (or m == 0 for the encode) returns QFEC_OK and
+ *     launches nothing.
+ *   qfec_set_kernel_variant does not apply: always the perm-table kernels. */
+int qfec_encode_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                     long long groups, int block_size, void *stream);
+int qfec_reconstruct_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                          const unsigned char *d_marks, long long groups, int block_size,
+                          unsigned int *d_failed, void *stream);
+
 /* Host-side decode-matrix query for one group (group-order marks[n]).  Writes e <= m
  * rows of k coefficients over the survivors listed in survivors[k] (shard ids 0..n-1).
  * Returns e, 0 when nothing is erased, or -1 when under-determined.  CPU only. */
@@ -540,6 +577,12 @@ int qfec_probe_reconstruct(unsigned char *d_data, const unsigned char *d_parity,
  *                      caller shards for module/rs.h on host pointers)
  *   "host_threads"     host threads that gather / scatter module/rs.h host shard pointers (0: the
  *                      CPUs this process may use -- affinity and cgroup quota -- at most 32)
+ *   "rs_dev_ptrs"      0 (default) | 1: module/rs.h on shard arrays that are all device memory but not
+ *                      back to back: 1 sends the pointer array to the device (one copy per chunk) and
+ *                      runs the qfec_*_ptrs kernels on the caller's rows in place; 0 stages every row
+ *                      through one copy in and one copy out.  Results and return codes are the same.
+ *                      Host or mixed arrays, contiguous arrays and k + m > 24 (reconstruct) are not
+ *                      affected
  *   "percall_resident" 1 fec_encode / fec_decode of packets up to 4 KiB with k <= 16 and k * e <= 64
  *                      go to a resident one-block server that polls a request word in device memory
  *                      and exits by itself after percall_idle_us without a request | 0 one launch per

@@ -18,7 +18,7 @@ EXPORTS = {
     "qfec.h": ["qfec_code_new", "qfec_code_from_rows", "qfec_code_free", "qfec_code_rows", "qfec_code_shape",
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
-               "qfec_encode_update", "qfec_update",
+               "qfec_encode_update", "qfec_update", "qfec_encode_ptrs", "qfec_reconstruct_ptrs",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
                "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
@@ -85,6 +85,8 @@ def lib():
         "qfec_verify": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_encode_update": (i, [vp, i, i, vp, vp, ll, i, ll, i, vp]),
         "qfec_update": (i, [vp, vp, vp, vp, vp, ll, i, ll, vp, vp]),
+        "qfec_encode_ptrs": (i, [vp, vp, ll, i, vp]),
+        "qfec_reconstruct_ptrs": (i, [vp, vp, vp, ll, i, vp, vp]),
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),

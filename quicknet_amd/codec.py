@@ -271,6 +271,31 @@ class Code:
                                      _dev_ptr(marks, what="marks"), G, block_size, pitch,
                                      _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_reconstruct")
 
+    def _ptr_groups(self, what, ptrs):
+        n = self.k + self.m
+        if ptrs.dim() != 1 or ptrs.numel() % n:
+            raise QfecError(f"{what}: {tuple(ptrs.shape)} pointers are not groups * (k + m) = groups * {n}")
+        return ptrs.numel() // n
+
+    def encode_ptrs(self, ptrs, block_size, stream=None):
+        """qfec_encode_ptrs: encode shards scattered in device memory.  ptrs: 1-D int64 device tensor of
+        groups * (k + m) device addresses in rs.c's shard order -- every group's k data shards, then
+        every group's m parity shards; each shard is exactly block_size bytes, at any alignment."""
+        G = self._ptr_groups("encode_ptrs", ptrs)
+        check(lib().qfec_encode_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
+                                     _stream_handle(stream)), "qfec_encode_ptrs")
+
+    def reconstruct_ptrs(self, ptrs, marks, block_size, failed=None, stream=None):
+        """qfec_reconstruct_ptrs: rewrite the marked data shards in place where they lie.  ptrs as for
+        encode_ptrs; marks: uint8 [G*k + G*m] (rs.c layout) on device; failed: optional device
+        int32/uint32 [1] counter of under-determined groups (accumulates)."""
+        G = self._ptr_groups("reconstruct_ptrs", ptrs)
+        if marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"reconstruct_ptrs: {marks.numel()} marks for {G} groups of ({self.k},{self.m})")
+        check(lib().qfec_reconstruct_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(marks, what="marks"), G,
+                                          int(block_size), _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)),
+              "qfec_reconstruct_ptrs")
+
     def prepare_repair(self):
         check(lib().qfec_prepare_repair(self._h), "qfec_prepare_repair")
 

@@ -6,7 +6,8 @@
 // the layout is not 16-B aligned, (group, column) flattened over the grid.  8-byte lanes
 // (reconstruct, repair, locate_erased): a wave covers 64 8-byte columns of one group, wpg8 waves
 // per group.  qfec_update has whole waves per group too, on 16-B columns (WaveGeom); the range form
-// qfec_encode_update is flat.  In all of them no launch has more than 2^31 - 1 lanes; a larger batch goes in several
+// qfec_encode_update is flat; the pointer-table calls have whole waves per group as well (PtrsGeom).
+// In all of them no launch has more than 2^31 - 1 lanes; a larger batch goes in several
 // launches over consecutive groups (for_group_chunks).
 #pragma once
 
@@ -72,6 +73,31 @@ inline WaveGeom wave_geom(const FlatGeom& f) {
     w.wpg = (w.cols + 63) / 64;
     w.per = std::max<long long>(1, kMaxLaunchLanes / (64ll * std::max(w.wpg, 1u)));
     return w;
+}
+
+// The pointer-table calls (qfec_encode_ptrs, qfec_reconstruct_ptrs): a shard is exactly `block`
+// bytes with nothing usable after it.  A wave covers 64 columns of lane_bytes (16 or 8) of one group.
+// The whole columns go to the vector body; the block % lane_bytes bytes after them go byte by byte
+// to the first lanes of the group's last wave, which always exists: wpg counts the part column.
+// A group whose pointers are not all 16-B aligned runs the same waves over the same spans byte by byte.
+struct PtrsGeom {
+    uint32_t vcols, wpg;    // whole columns per shard; waves per group
+    uint32_t tail0, tailn;  // first byte and count of the tail (tailn < lane_bytes; tail0 + tailn = block)
+    long long per;          // groups per launch
+};
+
+// 16-B lanes, except the reconstruct of k >= 10 on 8-B lanes, where the contiguous reconstruct's
+// auto body runs them too (its 16-B body holds k inputs of four registers each: 4 waves per SIMD)
+inline int ptrs_lane_bytes(bool reconstruct, int k) { return reconstruct && k >= 10 ? 8 : 16; }
+
+inline PtrsGeom ptrs_geom(int block, int lane_bytes) {
+    PtrsGeom p;
+    p.vcols = (uint32_t)(block / lane_bytes);
+    p.tail0 = p.vcols * (uint32_t)lane_bytes;
+    p.tailn = (uint32_t)block - p.tail0;
+    p.wpg = (p.vcols + (p.tailn ? 1u : 0u) + 63) / 64;
+    p.per = std::max<long long>(1, kMaxLaunchLanes / (64ll * std::max(p.wpg, 1u)));
+    return p;
 }
 
 // fn(g0, gn) once per launch, over [g0, g0 + gn) ascending; stops at the first non-zero return

@@ -150,6 +150,27 @@ struct UpdateArgs {
     int vec16;
 };
 
+// encode / reconstruct on a table of shard addresses (qfec_ptrs.hip): one wave per (group, slab of 64
+// columns); every shard is exactly `block` bytes and no byte outside it is touched
+struct PtrsArgs {
+    const uint64_t* dptrs;    // [groups][k] addresses of the data shards of this launch's groups
+    const uint64_t* pptrs;    // [groups][m] addresses of their parity shards
+    const uint8_t* dmarks;    // reconstruct: [groups][k] data marks of this launch's groups
+    const uint8_t* pmarks;    // reconstruct: [groups][m] parity marks
+    const uint32_t* tab;      // encode: [m][k][QFEC_TAB_STRIDE]
+    const int32_t* lut;       // reconstruct: [2^n] pattern -> record offset (dwords) / QFEC_REC_*
+    const uint32_t* records;
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    unsigned int* failed;
+    uint64_t groups;
+    uint32_t block;           // bytes per shard
+    uint32_t lane_bytes;      // 16 or 8: bytes per lane of the vector body (PtrsGeom)
+    uint32_t vcols, wpg;      // whole lane_bytes columns per shard; waves per group
+    uint32_t tail0, tailn;    // the bytes past the last whole column: first byte, count (< lane_bytes)
+    int k, m;
+    int surv_off, lost_off, hdr, coff;  // RecordLayout
+};
+
 // single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
 // syndrome tests every data shard as the culprit
 struct LocateArgs {
@@ -341,6 +362,7 @@ struct Tuning {
     std::atomic<int> host_nt{2};        // module/rs.h on host pointers: streaming stores into the slots (0 / 1 / 2 sequential rows)
     std::atomic<int> encode_block{-1};  // threads per encode block: -1 auto (64 for k = 10 all-rows), 64, 256
     std::atomic<int> encode_lds{-1};    // LDS bytes per encode block, capping waves per CU (-1 auto, 0 none)
+    std::atomic<int> rs_dev_ptrs{0};    // module/rs.h on scattered device shards: 1 the pointer-table kernels in place, 0 staged copies
 };
 Tuning& tuning();
 
@@ -350,6 +372,8 @@ hipError_t launch_repair(const RepairArgs& a, hipStream_t stream);
 hipError_t launch_verify(const VerifyArgs& a, hipStream_t stream);
 hipError_t launch_encode_update(const EncUpdateArgs& a, hipStream_t stream);
 hipError_t launch_update(const UpdateArgs& a, hipStream_t stream);
+hipError_t launch_encode_ptrs(const PtrsArgs& a, hipStream_t stream);
+hipError_t launch_reconstruct_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);

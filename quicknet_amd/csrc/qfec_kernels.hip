@@ -64,21 +64,7 @@ __global__ void __launch_bounds__(256) k_encode_perm(EncodeArgs a) {
         acc[r] = make_uint4(0, 0, 0, 0);
         if (tab[(r * K) * QFEC_TAB_STRIDE + 5]) acc[r] = *reinterpret_cast<const uint4*>(dst + (uint64_t)r * a.pitch);
     }
-#pragma unroll
-    for (int c = 0; c + 1 < K; c += 2) {
-        Sel sa[4], sb[4];
-        sel16(sa, x[c]);
-        sel16(sb, x[c + 1]);
-#pragma unroll
-        for (int r = 0; r < M; ++r)
-            gf_mac16x2(acc[r], sa, sb, tab + (r * K + c) * QFEC_TAB_STRIDE, tab + (r * K + c + 1) * QFEC_TAB_STRIDE);
-    }
-    if (K & 1) {
-        Sel s[4];
-        sel16(s, x[K - 1]);
-#pragma unroll
-        for (int r = 0; r < M; ++r) gf_mac16(acc[r], s, tab + (r * K + K - 1) * QFEC_TAB_STRIDE);
-    }
+    enc_mac16<K, M, 0, K>(acc, x, tab);
 #pragma unroll
     for (int r = 0; r < M; ++r) st16(dst + (uint64_t)r * a.pitch, acc[r]);
 }
@@ -275,69 +261,10 @@ __device__ __forceinline__ int group_record(const ReconArgs& a, uint64_t g, int 
     return __builtin_amdgcn_readfirstlane(rec);
 }
 
-// Exactly E rows (E = the group's erased-data count, wave-uniform): all E rows at once,
-// selectors formed once per input and shared by the rows, no work on the M - E rows a group
-// does not need.  3 random erasures of 13 give e = 1, 2, 3
-// with probability 0.10, 0.47, 0.42, so RS(10,3) does 77 % of the all-rows VALU work.
-// D = dwords per lane (4: 16-B columns, 2: 8-B columns for rows whose 16-B column count
-// leaves a wave mostly idle, e.g. B = 1400: 88 16-B columns on 2 waves, 175 8-B on 3).
-template <int D>
-__device__ __forceinline__ void stv(uint8_t* p, const uint32_t (&v)[D]) {
-    if constexpr (D == 4) {
-        const u32x4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
-    } else if constexpr (D == 3) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(p);
-        __builtin_nontemporal_store(v[0], q);
-        __builtin_nontemporal_store(v[1], q + 1);
-        __builtin_nontemporal_store(v[2], q + 2);
-    } else {
-        const u32x2 t = {v[0], v[1]};
-        __builtin_nontemporal_store(t, reinterpret_cast<u32x2*>(p));
-    }
-}
-template <int D>
-__device__ __forceinline__ void ldv_plain(uint32_t (&v)[D], const uint8_t* p) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) v[d] = reinterpret_cast<const uint32_t*>(p)[d];
-}
-
-template <int K, int E, int D>
-__device__ __forceinline__ void recon_column_e(const uint8_t* const (&src)[K], uint8_t* __restrict__ data_g,
-                                               uint64_t lost_bits, const RTab& T, uint64_t pitch, uint64_t off) {
-    uint32_t x[K][D];
-#pragma unroll
-    for (int c = 0; c < K; ++c) ldv<D>(x[c], src[c] + off);
-    uint8_t* dst[E];
-    uint32_t acc[E][D];
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(lost_bits);
-        lost_bits &= lost_bits - 1;
-        dst[j] = data_g + (uint64_t)l * pitch + off;
-#pragma unroll
-        for (int d = 0; d < D; ++d) acc[j][d] = 0;
-        if (T.quirk(j, K)) ldv_plain<D>(acc[j], dst[j]);  // rs.c column-0 quirk
-    }
-    recon_mac_core<K, E, D>(x, acc, T);
-#pragma unroll
-    for (int j = 0; j < E; ++j) stv<D>(dst[j], acc[j]);
-}
-
-// wave-uniform dispatch on e to the exact-row-count body
-template <int K, int M, int D, int E = M>
-__device__ __forceinline__ void recon_column_by_e(const uint8_t* const (&src)[K], uint8_t* __restrict__ data_g,
-                                                  uint64_t lost_bits, const RTab& T, int e, uint64_t pitch, uint64_t off) {
-    if constexpr (E > 1) {
-        if (e < E) {
-            recon_column_by_e<K, M, D, E - 1>(src, data_g, lost_bits, T, e, pitch, off);
-            return;
-        }
-    }
-    recon_column_e<K, E, D>(src, data_g, lost_bits, T, pitch, off);
-}
-
-// LUT mode, compile-time K, M.  The survivor set follows from the erasure mask alone --
+// The column body (exactly E rows for a group with E erased data shards) is recon_column_by_e in
+// qfec_device.hpp, shared with the pointer-table kernels.
+//
+// LUT mode, compile-time K, M. The survivor set follows from the erasure mask alone --
 // it is the lowest K non-erased shard ids (all surviving data, then the first e surviving
 // parity rows: module/rs.c:620-629) -- so the shard loads issue right after the ballot,
 // while the decode record (coefficients only) is still in flight.
@@ -382,9 +309,10 @@ __device__ __forceinline__ void recon_item(const ReconArgs& a, uint8_t* __restri
     }
     const uint32_t col = part * 64u + lane;
     if (col < (IMPL == 3 ? a.cols8 : IMPL == 4 ? a.cols12 : a.cols)) {
-        if (IMPL == 2) recon_column_by_e<K, M, 4>(src, data_g, lost_bits, T, e, pitch, (uint64_t)col * 16u);
-        else if (IMPL == 3) recon_column_by_e<K, M, 2>(src, data_g, lost_bits, T, e, pitch, (uint64_t)col * 8u);
-        else recon_column_by_e<K, M, 3>(src, data_g, lost_bits, T, e, pitch, (uint64_t)col * 12u);
+        const RowsAt rows{pitch};
+        if (IMPL == 2) recon_column_by_e<K, M, 4>(src, data_g, rows, lost_bits, T, e, (uint64_t)col * 16u);
+        else if (IMPL == 3) recon_column_by_e<K, M, 2>(src, data_g, rows, lost_bits, T, e, (uint64_t)col * 8u);
+        else recon_column_by_e<K, M, 3>(src, data_g, rows, lost_bits, T, e, (uint64_t)col * 12u);
     }
 }
 

@@ -1,7 +1,8 @@
 // qfec_rs_abi.cpp -- module/rs.h on the GPU: reed_solomon_init / new / release / encode /
 // reconstruct / error (module/rs.h:22-49, module/rs.c:387-643).  Every caller shard pointer is
-// classified; arrays of host pointers run the two-slot pipelines below, device arrays run in place,
-// mixes are staged row by row.
+// classified; arrays of host pointers run the two-slot pipelines below, contiguous device arrays run
+// in place, scattered device arrays are staged row by row or, with tuning "rs_dev_ptrs", handed to
+// the pointer-table kernels as they are; mixes are staged row by row.
 #include "qfec_rt.hpp"
 
 #include <immintrin.h>
@@ -166,6 +167,50 @@ void staged_report(const char* what, size_t ndev, size_t nptr) {
     if (getenv("QFEC_RS_TRACE"))
         fprintf(stderr, "[qfec] %s: %.2f ms in the call (classify %.2f ms); %zu of %zu pointers device memory\n", what,
                 RsTrace::since(t_rs_entry) * 1e3, t_rs_classify * 1e3, ndev, nptr);
+}
+
+// Tuning "rs_dev_ptrs" = 1, every shard in device memory but not back to back: the kernels of
+// qfec_ptrs.hip work on the caller's rows where they lie.  Per chunk of `per` groups the chunk's
+// addresses -- and, for the reconstruct (mk non-null), its marks -- go through the pinned stage in
+// the chunk's own rs.c layout with one H2D copy; every chunk has its own part of the stage, so
+// nothing waits before the one synchronisation at the end.  *nfail (reconstruct) is the device's
+// count of under-determined groups, read back after it.  Caller holds ctx.mu.
+int rs_ptrs_path(DevCtx& ctx, qfec_code* c, const uint32_t* tab, const DevLut* dec, unsigned char** data,
+                 unsigned char** par, const uint8_t* mk, long long G, int B, long long per, long long* nfail) {
+    const int k = c->k, m = c->m, n = k + m;
+    const size_t per_group = round_up((size_t)n * 8 + (mk ? (size_t)n : 0), 8);
+    const size_t tot = (size_t)G * per_group + 8 * (size_t)((G + per - 1) / per);
+    int rc = ensure_stage(ctx, tot, tot);
+    if (rc) return rc;
+    if (mk) HIP_TRY(hipMemsetAsync(ctx.d_counter, 0, 4, ctx.stream));
+    size_t at = 0;
+    for (long long g0 = 0; g0 < G; g0 += per) {
+        const long long gn = std::min(per, G - g0);
+        const size_t pbytes = (size_t)gn * n * 8, bytes = round_up(pbytes + (mk ? (size_t)gn * n : 0), 8);
+        uint8_t* hs = ctx.h_stage + at;
+        uint8_t* ds = ctx.d_stage + at;
+        memcpy(hs, data + g0 * k, (size_t)gn * k * 8);
+        memcpy(hs + (size_t)gn * k * 8, par + g0 * m, (size_t)gn * m * 8);
+        if (mk) {
+            memcpy(hs + pbytes, mk + (size_t)g0 * k, (size_t)gn * k);
+            memcpy(hs + pbytes + (size_t)gn * k, mk + (size_t)G * k + (size_t)g0 * m, (size_t)gn * m);
+        }
+        HIP_TRY(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, ctx.stream));
+        const uint64_t* dp = reinterpret_cast<const uint64_t*>(ds);
+        const uint64_t* pp = dp + (size_t)gn * k;
+        rc = mk ? run_reconstruct_ptrs(ctx, c, *dec, dp, pp, ds + pbytes, ds + pbytes + (size_t)gn * k, gn, B,
+                                       ctx.d_counter, ctx.stream)
+                : run_encode_ptrs(c, tab, dp, pp, gn, B, ctx.stream);
+        if (rc) break;
+        at += bytes;
+    }
+    unsigned failed = 0;
+    if (!rc && mk && hipMemcpyAsync(&failed, ctx.d_counter, 4, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
+        rc = hip_fail(hipGetLastError(), "module/rs.h on device pointers: reading the failed count");
+    if (hipStreamSynchronize(ctx.stream) != hipSuccess && !rc)
+        rc = hip_fail(hipGetLastError(), "module/rs.h on device pointers: synchronise");
+    if (nfail) *nfail = failed;
+    return rc;
 }
 
 // bytes of caller shards per pipelined chunk of the host-pointer paths (tuning "host_chunk"
@@ -710,8 +755,9 @@ int reed_solomon_encode(reed_solomon* rs, unsigned char** shards, int nr_shards,
     unsigned char** data = shards;
     unsigned char** par = shards + G * k;
     // every shard pointer is classified: all host -> the pipelined host path, all device and
-    // contiguous -> in place, otherwise staged by kind (host rows through the pinned stage, device
-    // rows one copy each)
+    // contiguous -> in place, all device and scattered with tuning "rs_dev_ptrs" -> the pointer-table
+    // kernels in place, otherwise staged by kind (host rows through the pinned stage, device rows
+    // one copy each)
     const size_t nptr = (size_t)G * n;
     const auto tc = std::chrono::steady_clock::now();
     std::shared_ptr<HostPool> pool = host_pool();
@@ -733,6 +779,12 @@ int reed_solomon_encode(reed_solomon* rs, unsigned char** shards, int nr_shards,
     const size_t pitch = round_up((size_t)block_size, 16);
     const long long per = tuning().host_chunk > 0 ? (long long)tuning().host_chunk
                                                   : std::max<long long>(1, (long long)(kChunkBytes / ((size_t)n * pitch)));
+    if (ndev == nptr && tuning().rs_dev_ptrs) {
+        rc = rs_ptrs_path(*ctx, c, tab, nullptr, data, par, nullptr, G, block_size, per, nullptr);
+        if (rc) fprintf(stderr, "[qfec] reed_solomon_encode: %s\n", qfec_last_error());
+        staged_report("reed_solomon_encode (ptrs)", ndev, nptr);
+        return rc;
+    }
     for (long long g0 = 0; g0 < G && !rc; g0 += per) {
         const long long gn = std::min(per, G - g0);
         const size_t dbytes = (size_t)gn * k * pitch, pbytes = (size_t)gn * m * pitch;
@@ -820,6 +872,24 @@ int reed_solomon_reconstruct(reed_solomon* rs, unsigned char** shards, unsigned 
     const size_t pitch = round_up((size_t)block_size, 16);
     const long long per = tuning().host_chunk > 0 ? (long long)tuning().host_chunk  // knob: tests force several chunks
                                                   : std::max<long long>(1, (long long)(kChunkBytes / ((size_t)n * pitch)));
+    if (tuning().rs_dev_ptrs && n <= QFEC_LUT_MAX_N && ndev_all == (size_t)G * n &&
+        !(contiguous(data, (size_t)G * k, block_size) && contiguous(par, (size_t)G * m, block_size))) {
+        DevTables* d = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            rc = ensure_lut(c, ctx->device, &d);
+        }
+        if (!rc) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            rc = rs_ptrs_path(*ctx, c, nullptr, &d->dec, data, par, mk, G, block_size, per, &nfail_all);
+        }
+        staged_report("reed_solomon_reconstruct (ptrs)", ndev_all, (size_t)G * n);
+        if (rc) {
+            fprintf(stderr, "[qfec] reed_solomon_reconstruct: %s\n", qfec_last_error());
+            return rc;
+        }
+        return nfail_all ? -1 : 0;
+    }
     std::vector<uint8_t> cmarks, only;
     std::vector<int32_t> grec;
     std::vector<uint32_t> recs;

@@ -13,6 +13,7 @@
 //   qfec_locate_erased.cpp  qfec_locate_erased (its LUT and records), qfec_scrub_erased
 //   qfec_locate2.cpp   qfec_locate2 (its acceptance check and pair constants), qfec_scrub2
 //   qfec_update.cpp    qfec_encode_update, qfec_update (incremental parity on the encode's tables)
+//   qfec_ptrs.cpp      qfec_encode_ptrs, qfec_reconstruct_ptrs (shards given as a device table of addresses)
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
@@ -252,6 +253,13 @@ int run_reconstruct(DevCtx& ctx, const qfec_code* c, const int32_t* lut, const i
                     const uint32_t* recs, uint8_t* d_data, const uint8_t* d_par, const uint8_t* d_marks,
                     long long groups, int block, long long pitch, unsigned* d_failed, hipStream_t s,
                     long long dgs = -1, long long pgs = -1);
+// the pointer-table kernels (qfec_ptrs.cpp): dptrs / pptrs are device arrays of groups * k and
+// groups * m shard addresses, dmarks / pmarks the two halves of rs.c-layout marks
+int run_encode_ptrs(const qfec_code* c, const uint32_t* tab, const uint64_t* dptrs, const uint64_t* pptrs,
+                    long long groups, int block, hipStream_t s);
+int run_reconstruct_ptrs(DevCtx& ctx, const qfec_code* c, const DevLut& dec, const uint64_t* dptrs,
+                         const uint64_t* pptrs, const uint8_t* dmarks, const uint8_t* pmarks, long long groups,
+                         int block, unsigned* d_failed, hipStream_t s);
 int host_records(qfec_code* c, const uint8_t* marks, long long groups, std::vector<int32_t>& grec,
                  std::vector<uint32_t>& recs, long long* nfail);
 int reconstruct_host_records(DevCtx& ctx, qfec_code* c, uint8_t* d_data, const uint8_t* d_par,

@@ -667,6 +667,7 @@ const std::vector<Knob>& knob_table() {
         {"percall_resident", &g_percall_resident, 0, 1},
         {"encode_lds", &tuning().encode_lds, -1, 163840},
         {"encode_block", &tuning().encode_block, -1, 256},
+        {"rs_dev_ptrs", &tuning().rs_dev_ptrs, 0, 1},
     };
     return t;
 }
