@@ -463,7 +463,20 @@ int qfec_fec_matrix(void *fec_handle, unsigned char *out_full);
  * Layout: d_shards [G][n][shard_pitch], d_wire [G][n][wire_pitch] (16-B aligned, pitches
  * multiples of 16, wire_pitch >= shard_pitch + 13), d_wire_len [G*n] (0 = not received),
  * d_marks [G*n] rs.c-layout scratch, d_rx_size [G*n] (nullable).  n = k + m <= 15 (the
- * header's 4-bit fields).  d_payload must stay readable 16 bytes past its last byte. */
+ * header's 4-bit fields).  d_payload must stay readable 16 bytes past its last byte.
+ * Send, what a call leaves behind (qfec_pack_datagrams; qfec_pack_frames follows it):
+ *   - a group with any size < 0 or > shard_pitch - head (head = 4 with checksums, 2 without) is
+ *     void: all its n d_wire_len entries are -1.  The test is size <= shard_pitch - head, so sizes
+ *     up to INT_MAX are void too.  Every row of a void group is either left as the caller had it or
+ *     all zero.  The offsets of a void group's rows are still dereferenced on the staged path
+ *     (k_build_shards reads up to shard_pitch bytes behind them) and so must be valid.
+ *   - bytes [d_wire_len, wire_pitch) of a live row are zero where the fused send stores whole 64-B
+ *     lines: a templated (k, m), wire_pitch the 64-B multiple just above hdr + shard_pitch (hdr = 13
+ *     with checksums, 11 without) and at least 320 B (checksums) / 256 B (none).  Elsewhere each such
+ *     byte is zero or left as the caller had it; nothing else is written there.
+ *   - d_shards is scratch: the staged path builds the shards in it, the fused send keeps 16-lane
+ *     partial byte sums there (never more than groups * n * shard_pitch bytes), or leaves it alone.
+ *   - no input is written. */
 int qfec_pack_datagrams(qfec_code *code, const unsigned char *d_payload, const long long *d_offsets,
                         const int *d_sizes, const unsigned int *d_seq, long long groups, int checksum,
                         unsigned char *d_shards, long long shard_pitch, unsigned char *d_wire,
@@ -502,10 +515,14 @@ int qfec_unframe_udp(const unsigned char *d_in, long long in_pitch, const int *d
  * [mask][c][(cmd & 0x1f) | 0xA0][protocol]([conv][hid])[datagram (g, j)], bytes 1.. XORed with
  * d_mask[g*n+j] ^ gmask ^ 0x5a; d_frame_len[g*n+j] = framed length (-1 for a void group).
  * The Session prefix is present iff d_conv_hid ([G*n][2]) is non-NULL.  Bytes of a row past its
- * frame, up to frame_pitch, are zero.  One pass (no datagram buffer in HBM) with checksums on, a
- * templated (k, m) and frame_pitch = 1088 or 576 equal to the 64-B multiple above prefix + 13 +
- * shard_pitch (1 KiB / 512-B payloads); other cases run the two calls over stream-ordered scratch.
- * d_shards is scratch as in qfec_pack_datagrams.
+ * frame, up to frame_pitch, are zero (every path); every row of a void group is left as the caller
+ * had it (one pass) or all zero (two calls).  d_mask may have any alignment (the one pass reads it
+ * in dwords counted from d_mask: up to 3 bytes past the G*n masks are read, and ignored).
+ * One pass (no datagram buffer in HBM) with checksums on, a templated (k, m) and frame_pitch equal to
+ * the 64-B multiple above prefix + 13 + shard_pitch, where that is 576 (512-B payloads: two groups
+ * per wave), 1088 (1 KiB payloads), 1152..1600 (8-B lanes, three passes: 1400-B payloads) or
+ * 1664..2112 (16-B lanes, two passes); other cases run the two calls over stream-ordered scratch.
+ * d_shards is scratch as in qfec_pack_datagrams; sizes, void groups and their offsets as there.
  * qfec_unpack_frames = qfec_unframe_udp (ProtocolUdp::RecvPacket, ProtocolBasic.cpp:155-199) of
  * every row, rows RecvPacket rejects counting as not received, then qfec_unpack_datagrams over
  * the datagrams inside: the same d_marks / d_rx_size / d_status / d_psize / d_shards as that

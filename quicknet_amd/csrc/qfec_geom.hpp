@@ -100,6 +100,97 @@ inline PtrsGeom ptrs_geom(int block, int lane_bytes) {
     return p;
 }
 
+// The datagram / frame send (qfec_pack_datagrams, qfec_pack_frames; kernels in qfec_wire.hip): which
+// kernels a call takes.  `row_pitch` is the wire pitch, or the frame pitch with a frame prefix (4, or
+// 12 with the Session words); `instance`: a compile-time (k, m) exists and the fused send is on.
+//   line          the row pitch is the 64-B multiple just above the longest row (prefix + header +
+//                 shard pitch) and holds at least 20 chunks of 16 B (16 without checksums): every 64-B
+//                 line of a row is then stored whole, zeros past the datagram
+//   one wave per group (checksums on, line): 1088 B one pass of 16-B lanes; 576 B two groups per wave;
+//                 1104..1600 B three passes of 8-B lanes; frames only, 1664..2112 B: two passes of 16-B lanes
+//   body forms    flat over (group, chunk), lpg lanes per group covering chunks [ts, tn); with
+//                 checksums a second launch writes line 0 (line) or chunk 0 and byte 16 (k_pack_head),
+//                 from the 16-lane partial sums the body leaves in d_shards
+//   frames        take one wave per group or the two calls, never a body form
+enum SendKind {
+    kSendStaged = 0,  // build -> encode -> emit
+    kSendWave1,
+    kSendWave2,
+    kSendWave8x3,
+    kSendWave16x2,
+    kSendBodyLine0,
+    kSendBodyHead,
+    kSendBody11Line,
+    kSendBody11,
+    kSendTwoCall,  // frames: qfec_pack_datagrams into scratch, then qfec_frame_udp
+};
+
+struct SendForm {
+    int kind;
+    bool line;
+    uint32_t gpw;        // one wave per group: groups per wave (else 0)
+    uint32_t ts, tn;     // body forms: chunks [ts, tn) of a row (else 0)
+    uint32_t lpg;        // body forms: lanes per group, at least 16 (else 0)
+    uint32_t rec_words;  // u32 per 16-lane row of the body that it writes into d_shards (0: none)
+    uint64_t per;        // groups per launch (pair); a multiple of 16 for the body forms, so that
+                         // g0 * lpg % 16 == 0 and a launch's first 16-lane row is a whole one
+};
+
+inline int send_wave_kind(uint64_t row_pitch) {
+    // above 1088 B: 8-B lanes in three passes (1472 B, RS(10,13) x 100k: 737 against 781 us for
+    // the body + line-0 pair); at 1088 B 16-B lanes, one pass (497 against 545 us on 8-B lanes).
+    // (16-B lanes in two passes above 1088 B, a retired A/B, ran 841 us against 782 for the body +
+    // line-0 pair at 1472 B: profiles/r03_wire/r03n_mtu_ab.txt)
+    if (row_pitch > 1088 && row_pitch <= 1600) return kSendWave8x3;
+    if (row_pitch == 576) return kSendWave2;
+    if (row_pitch == 1088) return kSendWave1;
+    return kSendStaged;
+}
+
+inline SendForm send_form(bool instance, int n, int checksum, uint64_t pitch, uint64_t row_pitch, int prefix) {
+    SendForm f{};
+    f.per = 1;
+    if (prefix) {
+        // frames above 1088 B take the two-pass wave whenever the one-wave send is on: the other way
+        // is two calls (datagrams, then frames), 1 577 against 851 us at 1472 B (r03n)
+        int w = send_wave_kind(row_pitch);
+        if (!w && row_pitch > 1088 && row_pitch <= 2112) w = kSendWave16x2;
+        f.kind = kSendTwoCall;
+        if (!instance || !checksum || !w || row_pitch != ((uint64_t)prefix + 13 + pitch + 63) / 64 * 64) return f;
+        f.kind = w;
+    } else {
+        if (!instance) return f;
+        const uint64_t hdr = checksum ? 13 : 11;
+        f.line = row_pitch % 64 == 0 && row_pitch == (hdr + pitch + 63) / 64 * 64 && row_pitch / 16 >= (checksum ? 20u : 16u);
+        const int w = send_wave_kind(row_pitch);
+        if (checksum && f.line && w) {
+            f.kind = w;
+        } else {
+            f.kind = checksum ? (f.line ? kSendBodyLine0 : kSendBodyHead) : (f.line ? kSendBody11Line : kSendBody11);
+            // body lanes per group cover chunks [ts, tn): the longest datagram the shard pitch allows,
+            // or with `line` every chunk up to the pitch; chunk 0 (line: chunks 0-3) is the second launch's
+            f.ts = checksum ? (f.line ? 4u : 1u) : 0u;
+            f.tn = f.line ? (uint32_t)(row_pitch / 16) : (uint32_t)((hdr + pitch + 15) / 16);
+            f.lpg = std::max(16u, f.tn - f.ts);
+            f.rec_words = checksum ? 2u * (uint32_t)((n + 1) / 2) : 0u;
+            f.per = std::max<uint64_t>((((uint64_t)1 << 30) / f.lpg) & ~(uint64_t)15, 16);
+            return f;
+        }
+    }
+    f.line = true;
+    f.gpw = f.kind == kSendWave2 ? 2u : 1u;
+    f.per = (uint64_t)1 << 28;
+    return f;
+}
+
+// u32 words of d_shards the body of a checksummed body form writes for a batch of `groups`: groups lie
+// back to back in the flat lane space, one record of rec_words per 16-lane row (its first group's sums,
+// then its last group's).  Never more than the groups * n * pitch bytes d_shards has: rec_words <= n + 1
+// u32 per 16 lanes, lpg <= pitch / 16 + 2 and pitch >= 16 (tests/test_tx_model.py walks every pitch).
+inline uint64_t send_part_words(const SendForm& f, uint64_t groups) {
+    return (groups * f.lpg + 15) / 16 * f.rec_words;
+}
+
 // fn(g0, gn) once per launch, over [g0, g0 + gn) ascending; stops at the first non-zero return
 template <class F>
 inline int for_group_chunks(long long groups, long long per, F&& fn) {

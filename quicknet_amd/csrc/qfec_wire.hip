@@ -20,6 +20,7 @@
 
 #include <algorithm>
 
+#include "qfec_geom.hpp"
 #include "qfec_wire_device.hpp"
 
 namespace qfec {
@@ -86,8 +87,8 @@ __global__ void __launch_bounds__(256) k_emit_wire(WireArgs a) {
     bool ok = true;
     for (int i = 0; i < a.k; ++i) {
         const int sz = a.sizes[g * a.k + i];
-        ok = ok && sz >= 0 && sz + head <= (int)a.pitch;
-        gmax = max(gmax, sz + head);
+        ok = ok && sz >= 0 && sz <= (int)a.pitch - head;  // not sz + head <= pitch: sizes near INT_MAX
+        gmax = max(gmax, (int)((uint32_t)sz + (uint32_t)head));
     }
     if (!ok) {  // a size the shard pitch cannot hold: the group is not packed
         if (lane == 0) a.wire_len[slot] = -1;
@@ -320,8 +321,8 @@ __device__ __forceinline__ bool group_sizes(const int32_t* __restrict__ sizes, u
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         size[i] = sizes[g * K + i];
-        ok = ok && size[i] >= 0 && size[i] + HEAD <= pitch;
-        gmax = max(gmax, size[i] + HEAD);
+        ok = ok && size[i] >= 0 && size[i] <= pitch - HEAD;  // not size + HEAD <= pitch: sizes near INT_MAX
+        gmax = max(gmax, (int)((uint32_t)size[i] + HEAD));    // meaningful only where ok; no signed overflow
     }
     return ok;
 }
@@ -717,9 +718,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV ? W
 #pragma unroll
     for (int i = 0; i < K; ++i) off[i] = ok ? offsets[g * K + i] : 0;
     uint8_t* out_g = a.wire + g * (uint64_t)N * a.wire_pitch;
-    // FP: the group's N mask bytes, from the aligned dwords that hold them (scalar loads for
-    // GPW 1; an aligned dword never reaches past the page its first byte is on); row r's XOR
-    // word is formed where it is used, so no N registers stay live across the encode
+    // FP: the group's N mask bytes, from the dwords that hold them, counted from fs.mask (any
+    // alignment: the loads compile to vector loads, which take any address; with a 4-B aligned
+    // fs.mask a dword never reaches past the page its first byte is on, otherwise the last dword
+    // read may end up to 3 bytes past the group's masks); row r's XOR word is formed where it is
+    // used, so no N registers stay live across the encode
     uint32_t mw5[FP ? 5 : 1];
     int msh = 0;
     if constexpr (FP != 0) {
@@ -942,61 +945,43 @@ hipError_t launch_build_shards(const WireArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the one-wave send's mapping for a wire (or frame) pitch that is the 64-B multiple above the row:
-// 1 one group per wave, one pass (1088 B); 2 two groups per wave (576 B); 10 one group per wave on
-// 8-B lanes (1104..1600 B); 0 none.  (16-B lanes in two passes above 1088 B, a retired A/B, ran
-// 841 us against 782 for the body + line-0 pair at 1472 B: profiles/r03_wire/r03n_mtu_ab.txt)
-static int send_wave_gpw(uint64_t wire_pitch) {
-    // above 1088 B: 8-B lanes in three passes (1472 B, RS(10,13) x 100k: 737 against 781 us for
-    // the body + line-0 pair); at 1088 B 16-B lanes, one pass (497 against 545 us on 8-B lanes)
-    if (wire_pitch > 1088 && wire_pitch <= 1600) return 10;
-    if (wire_pitch == 576) return 2;
-    if (wire_pitch == 1088) return 1;
-    return 0;
-}
-
+// Which kernels a call takes, the lanes per group and the groups per launch are send_form's
+// (qfec_geom.hpp); the launchers below only follow it.
 template <int K, int M, int HDR>
 hipError_t pack_fused_shape(const WireArgs& a, const uint32_t* tab, uint32_t* part, hipStream_t s) {
-    // body lanes per group cover chunks [TS, tn): the longest datagram the shard pitch allows;
-    // groups are packed back to back (no rounding), partial sums go per 16-lane row.
-    // LINE (when the wire pitch is the 64-B multiple just above HDR + shard pitch): chunks
-    // [TS, wire_pitch / 16), so lanes per group is a multiple of 4 and every
-    // 64-B line of a row is one store instruction (a line written in two parts costs the
-    // memory a read-modify-write: tools/wrskel.hip, profiles/r02zn_wrskel.txt)
-    const bool line = a.wire_pitch % 64 == 0 &&
-                      a.wire_pitch == (HDR + a.pitch + 63) / 64 * 64 && a.wire_pitch / 16 >= (HDR == 13 ? 20u : 16u);
+    // groups are packed back to back in the body's lane space (no rounding), partial sums go per
+    // 16-lane row.  LINE: lanes per group is a multiple of 4 and every 64-B line of a row is one
+    // store instruction (a line written in two parts costs the memory a read-modify-write:
+    // tools/wrskel.hip, profiles/r02zn_wrskel.txt)
+    const SendForm f = send_form(true, K + M, HDR == 13, a.pitch, a.wire_pitch, 0);
+    const bool line = f.line;
     // one wave per group (k_pack_wave64): the body's chunks 4.. are 64 lanes at a 1088-B wire
-    // pitch (one pass), 32 at 576 B (two groups per wave), up to 128 in two passes above 1088 B
-    // (1472 B: 1400-B payloads)
-    const int gpw = send_wave_gpw(a.wire_pitch);
-    if (HDR == 13 && line && gpw) {
-        for (uint64_t g0 = 0; g0 < a.groups; g0 += ((uint64_t)1 << 28)) {
-            const uint64_t gn = std::min((uint64_t)1 << 28, a.groups - g0);
+    // pitch (one pass), 32 at 576 B (two groups per wave), up to 192 8-B chunks in three passes
+    // above 1088 B (1472 B: 1400-B payloads)
+    if (f.gpw) {
+        for_group_chunks((long long)a.groups, (long long)f.per, [&](long long c0, long long cn) {
+            const uint64_t g0 = (uint64_t)c0, gn = (uint64_t)cn;
             WireArgs b = a;
             b.wire = a.wire + g0 * (uint64_t)(K + M) * a.wire_pitch;
             b.wire_len = a.wire_len + g0 * (K + M);
-            const dim3 grid((unsigned)((gn + 4 * (gpw == 2 ? 2 : 1) - 1) / (4 * (gpw == 2 ? 2 : 1))));
-            if (gpw == 1)
+            const dim3 grid((unsigned)((gn + 4 * f.gpw - 1) / (4 * f.gpw)));
+            if (f.kind == kSendWave1)
                 hipLaunchKernelGGL((k_pack_wave64<K, M, 1>), grid, dim3(256), 0, s, b, a.payload, a.offsets + g0 * K,
                                    a.sizes + g0 * K, a.seq + 2 * g0, tab, gn, FrameSend{});
-            else if (gpw == 10)
+            else if (f.kind == kSendWave8x3)
                 hipLaunchKernelGGL((k_pack_wave64<K, M, 1, 0, 3, 8>), grid, dim3(256), 0, s, b, a.payload,
                                    a.offsets + g0 * K, a.sizes + g0 * K, a.seq + 2 * g0, tab, gn, FrameSend{});
             else
                 hipLaunchKernelGGL((k_pack_wave64<K, M, 2>), grid, dim3(256), 0, s, b, a.payload, a.offsets + g0 * K,
                                    a.sizes + g0 * K, a.seq + 2 * g0, tab, gn, FrameSend{});
-        }
+            return 0;
+        });
         return hipGetLastError();
     }
-    const uint32_t TS = HDR == 13 ? (line ? 4 : 1) : 0;
-    const uint32_t tn = line ? (uint32_t)(a.wire_pitch / 16) : (uint32_t)((HDR + a.pitch + 15) / 16);
-    const uint32_t lpg = std::max(16u, tn - TS);
+    const uint32_t lpg = f.lpg;
     const DivMagic lpg_div = make_div_magic(lpg);
-    // groups per body + head launch pair (keeps g0 * lpg % 16 == 0)
-    uint64_t per = (((uint64_t)1 << 30) / lpg) & ~(uint64_t)15;
-    per = std::max(per, (uint64_t)16);
-    for (uint64_t g0 = 0; g0 < a.groups; g0 += per) {
-        const uint64_t gn = std::min(per, a.groups - g0);
+    for_group_chunks((long long)a.groups, (long long)f.per, [&](long long c0, long long cn) {
+        const uint64_t g0 = (uint64_t)c0, gn = (uint64_t)cn;
         const uint32_t lanes = (uint32_t)(gn * lpg);  // the grid covers whole 16-lane rows past it
         const uint64_t row0 = g0 * lpg / 16;
         if (line)
@@ -1012,7 +997,8 @@ hipError_t pack_fused_shape(const WireArgs& a, const uint32_t* tab, uint32_t* pa
         else if (HDR == 13)
             hipLaunchKernelGGL((k_pack_head<K, M>), dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, s, a, a.sizes,
                                tab, (const uint32_t*)part, a.seq, a.wire, a.wire_len, g0, (uint32_t)gn, lpg, row0);
-    }
+        return 0;
+    });
     return hipGetLastError();
 }
 
@@ -1023,7 +1009,8 @@ hipError_t pack_fused_shape(const WireArgs& a, const uint32_t* tab, uint32_t* pa
                           : pack_fused_shape<KK, MM, 11>(a, tab, part, s);                                  \
     }
 
-// `part` needs pack_part_words(pitch, n) u32 per group; the caller's shard buffer holds it
+// `part` takes send_part_words(form, groups) u32 (qfec_geom.hpp), written by the checksummed body
+// forms only; the caller's shard buffer (groups * n * pitch bytes) always holds them
 hipError_t launch_pack_fused(const WireArgs& a, const uint32_t* tab, uint32_t* part, hipStream_t s, bool* launched) {
     *launched = false;
     if (!a.groups) return hipSuccess;
@@ -1043,19 +1030,18 @@ hipError_t launch_pack_fused(const WireArgs& a, const uint32_t* tab, uint32_t* p
 
 // qfec_pack_frames: datagrams and their ProtocolUdp frames in one pass (k_pack_wave64 with a
 // frame prefix) where the frame pitch is the 64-B multiple just above prefix + 13 + shard pitch
-// and a group fills a wave (1088 B) or half of one (576 B); *launched = false otherwise
+// and a group fills a wave (1088 B), half of one (576 B) or a wave in several passes (1152..2112 B:
+// send_form, qfec_geom.hpp); *launched = false otherwise
 template <int K, int M>
 hipError_t pack_frames_shape(const WireArgs& a, const FrameSend& fs, int fp, const uint32_t* tab, hipStream_t s,
                              bool* launched) {
     const uint64_t fpitch = a.wire_pitch;
-    // frames above 1088 B take the two-pass wave whenever the one-wave send is on: the other way
-    // is two calls (datagrams, then frames), 1 577 against 851 us at 1472 B (r03n)
-    int gpw = send_wave_gpw(fpitch);
-    if (!gpw && fpitch > 1088 && fpitch <= 2112) gpw = 5;
-    if (!a.checksum || !gpw || fpitch != (fp + 13 + a.pitch + 63) / 64 * 64) return hipSuccess;
+    const SendForm sf = send_form(true, K + M, a.checksum, a.pitch, fpitch, fp);
+    if (sf.kind == kSendTwoCall) return hipSuccess;
     *launched = true;
-    for (uint64_t g0 = 0; g0 < a.groups; g0 += ((uint64_t)1 << 28)) {
-        const uint64_t gn = std::min((uint64_t)1 << 28, a.groups - g0);
+    const int gpw = sf.kind == kSendWave8x3 ? 10 : sf.kind == kSendWave16x2 ? 5 : (int)sf.gpw;
+    for_group_chunks((long long)a.groups, (long long)sf.per, [&](long long c0, long long cn) {
+        const uint64_t g0 = (uint64_t)c0, gn = (uint64_t)cn;
         WireArgs b = a;
         b.wire = a.wire + g0 * (uint64_t)(K + M) * fpitch;
         b.wire_len = a.wire_len + g0 * (K + M);
@@ -1079,7 +1065,8 @@ hipError_t pack_frames_shape(const WireArgs& a, const FrameSend& fs, int fp, con
         else QFEC_PF(2, 12, 1);
 #undef QFEC_PF
 #undef QFEC_PF8
-    }
+        return 0;
+    });
     return hipGetLastError();
 }
 

@@ -75,7 +75,7 @@ int qfec_pack_datagrams(qfec_code* code, const unsigned char* d_payload, const l
     if (tuning().wire_fused) {
         bool launched = false;
         // the fused path never materialises shards; their buffer holds its partial sums
-        // ((wire_pitch + 63) / 256 + 2) * 8 u32 per group  <<  n * pitch bytes
+        // (send_part_words of qfec_geom.hpp: never more than groups * n * pitch bytes)
         hipError_t e = launch_pack_fused(a, tab, reinterpret_cast<uint32_t*>(d_shards), s, &launched);
         if (e != hipSuccess) return hip_fail(e, "pack_fused launch");
         if (launched) return QFEC_OK;
