@@ -195,6 +195,74 @@ int qfec_repair_rows(const qfec_code *code, const unsigned char *marks_n,
                      unsigned char *rows_out /* t*k */, int *survivors_out /* k */,
                      int *lost_out /* t */);
 
+/* Device-built decode plans: reconstruct and repair for ANY k + m, asynchronously.  The calls above
+ * take a group's decode matrix from a host-built table of 2^(k+m) entries (k + m <= 24), or, in
+ * qfec_reconstruct above that, from host inversions after a read-back of the marks.  Here the plan
+ * of every group is computed on the device from the group's marks, on the caller's stream: no LUT,
+ * no qfec_prepare_*, no read-back, no host synchronisation, no k + m limit.
+ *   Codes: any code qfec_code_new or qfec_code_from_rows accepts, narrow ones (k + m <= 24) included.
+ *     QFEC_EUNSUP for a code that carries an rs.c decode matrix (qfec_rs_code of a handle) which is
+ *     not [I; rows], i.e. an edited handle: rs.c's decode with a partially inverted matrix is not
+ *     reproduced here.  Checked on the host, once per version of the code.
+ *   Marks, layouts, pitch, stream and the scratch bytes in [block_size, round_up(block_size, 16)) are
+ *     exactly those of qfec_reconstruct / qfec_repair.  16-byte lanes when both bases and the pitch
+ *     allow, else byte by byte.  Batches beyond the 32-bit index space of a launch are cut into
+ *     several launches by the host, as elsewhere.
+ *   Per group in mode QFEC_PLAN_RECONSTRUCT, with e marked data shards: e = 0 untouched; e greater
+ *     than the surviving parity: untouched and counted into *d_failed (device counter, may be NULL;
+ *     accumulated, not reset); else every marked data row is rewritten exactly as qfec_reconstruct
+ *     rewrites it: the same survivor rule (rs.c:620-629), the same rows, and the column-0 stale-row
+ *     quirk when the code has rs_stale_quirk.
+ *   Per group in mode QFEC_PLAN_REPAIR, with t marked shards: t = 0 untouched; t > m untouched and
+ *     counted; else data rows as above, and marked parity rows as true GF products, exactly as
+ *     qfec_repair / qfec_repair_rows define them.
+ *   A group whose survivor matrix is singular (explicit rows that are not MDS) is untouched and
+ *     counted, in either mode.
+ *   The plan of a group, qfec_plan_stride(code) bytes, public and fixed:
+ *       [0]   u16 t (rows to write), u16 e (of them erased data), u8 status (0 nothing to do, 1 work,
+ *             2 failed), pad to 16 bytes
+ *       [16]  k survivor ids (u8: the k lowest unmarked ids)
+ *             m lost ids (u8, the first t valid: data ascending, then parity as k + j; mode
+ *             RECONSTRUCT lists data only)
+ *             m stale flags (u8, 1: the row starts from the destination's previous bytes)
+ *       from the next 16-byte boundary: m x k coefficient bytes, the first t x k valid -- row j over the
+ *             survivors in the order listed
+ *       padded to a multiple of 16; every unused byte is zero.  With status 0 or 2 only t, e and the
+ *       status are set.
+ *   qfec_plan_build writes the plans of `groups` groups and counts the failed ones into *d_failed;
+ *     qfec_plan_apply executes plans on a batch and counts nothing.  It reads only the plan, never
+ *     the marks, so one plan may be applied to any number of batches with the same losses.  d_parity
+ *     is written only where the plan lists parity rows: under a RECONSTRUCT plan it is only read.  A
+ *     buffer that qfec_plan_build did not write is not a plan, and applying it is undefined.
+ *   d_plan must be 16-byte aligned (the stride is a multiple of 16, so every group's plan then is):
+ *     plans are written 16 bytes at a time and read as dwords.  Unlike a misaligned data base, which
+ *     only selects the byte path, a misaligned d_plan is refused with QFEC_EINVAL.
+ *   qfec_reconstruct_wide / qfec_repair_wide are qfec_plan_build into stream-ordered scratch followed
+ *     by qfec_plan_apply; the scratch is freed on the stream.  A batch is cut into launches so that
+ *     one chunk's plans stay under 64 MiB.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error: a null code, groups < 0, block_size < 1, pitch < block_size, mode not 0 or 1, a
+ *     null buffer with groups > 0 (d_failed may be NULL), a d_plan that is not 16-byte aligned.  groups == 0 returns QFEC_OK and launches
+ *     nothing.  Always the perm-table kernels (qfec_set_kernel_variant does not apply). */
+#define QFEC_PLAN_RECONSTRUCT 0   /* qfec_reconstruct's rule: erased data rows only            */
+#define QFEC_PLAN_REPAIR      1   /* qfec_repair's rule: every marked shard, data and parity   */
+long long qfec_plan_stride(const qfec_code *code);          /* bytes per group, a multiple of 16 */
+int qfec_plan_build(qfec_code *code, const unsigned char *d_marks, long long groups, int mode,
+                    unsigned char *d_plan /* [groups][stride] */, unsigned int *d_failed, void *stream);
+int qfec_plan_apply(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                    const unsigned char *d_plan, long long groups, int block_size, long long pitch,
+                    void *stream);
+int qfec_reconstruct_wide(qfec_code *code, unsigned char *d_data, const unsigned char *d_parity,
+                          const unsigned char *d_marks, long long groups, int block_size,
+                          long long pitch, unsigned int *d_failed, void *stream);
+int qfec_repair_wide(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                     const unsigned char *d_marks, long long groups, int block_size,
+                     long long pitch, unsigned int *d_failed, void *stream);
+/* The plan of one group (group-order marks[n]) in the same layout, stride bytes.  Any k + m.  CPU
+ * only, like qfec_repair_rows; QFEC_EINVAL / QFEC_EUNSUP as above. */
+int qfec_plan_build_host(const qfec_code *code, const unsigned char *marks_n, int mode,
+                         unsigned char *out_plan /* stride bytes */);
+
 /* Does the parity match the data?  Bit j of d_bad_rows[g] is set iff parity row j of group g
  * differs from rows[j] x data[g] (a true GF product) in any byte of [0, block_size); 0 = the group
  * is consistent.  d_bad_rows ([groups], may be NULL) is written for every group; *d_bad_groups

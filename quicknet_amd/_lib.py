@@ -19,6 +19,8 @@ EXPORTS = {
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
                "qfec_encode_update", "qfec_update", "qfec_encode_ptrs", "qfec_reconstruct_ptrs",
+               "qfec_plan_stride", "qfec_plan_build", "qfec_plan_apply", "qfec_reconstruct_wide", "qfec_repair_wide",
+               "qfec_plan_build_host",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
                "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
@@ -41,6 +43,7 @@ QFEC_VARIANT_LDSLOG = 1
 QFEC_LOC_CLEAN, QFEC_LOC_MULTI, QFEC_LOC_AMBIGUOUS = -1, -2, -3  # qfec_locate verdicts (include/qfec.h)
 QFEC_LOC_UNCHECKED, QFEC_LOC_LOST = -4, -5  # qfec_locate_erased: no spare row to check with; under-determined
 QFEC_UPD_NONE = -1  # qfec_update: this group is untouched
+QFEC_PLAN_RECONSTRUCT, QFEC_PLAN_REPAIR = 0, 1  # qfec_plan_build modes
 
 _lib = None
 
@@ -87,6 +90,12 @@ def lib():
         "qfec_update": (i, [vp, vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_encode_ptrs": (i, [vp, vp, ll, i, vp]),
         "qfec_reconstruct_ptrs": (i, [vp, vp, vp, ll, i, vp, vp]),
+        "qfec_plan_stride": (ll, [vp]),
+        "qfec_plan_build": (i, [vp, vp, ll, i, vp, vp, vp]),
+        "qfec_plan_apply": (i, [vp, vp, vp, vp, ll, i, ll, vp]),
+        "qfec_reconstruct_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
+        "qfec_repair_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
+        "qfec_plan_build_host": (i, [vp, vp, i, vp]),
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),

@@ -388,6 +388,75 @@ class Code:
                                 _dev_ptr(rows, what="rows"), _dev_ptr(parity, what="parity"), G, block_size, pitch,
                                 _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)), "qfec_update")
 
+    def plan_stride(self):
+        """Bytes per group of a decode plan (qfec_plan_stride), a multiple of 16."""
+        n = lib().qfec_plan_stride(self._h)
+        if n < 0:
+            check(int(n), "qfec_plan_stride")
+        return int(n)
+
+    def plan_build(self, marks, mode, plan=None, failed=None, stream=None):
+        """The decode plan of every group from its marks, on the device, for any k + m
+        (qfec_plan_build).  marks: uint8 [G*k + G*m] (rs.c layout) on device; mode:
+        QFEC_PLAN_RECONSTRUCT (erased data rows) or QFEC_PLAN_REPAIR (every marked shard).  Returns
+        plan, a device uint8 [G, plan_stride()] tensor (allocated when not given; one passed in must
+        start on a 16-byte boundary, which a slice of a tensor may not: the call refuses it otherwise);
+        failed: optional device int32/uint32 [1] counter of groups whose plan failed (accumulates)."""
+        import torch
+        n = self.k + self.m
+        if marks.numel() % n:
+            raise QfecError(f"plan_build: {marks.numel()} marks are not groups * (k + m) = groups * {n}")
+        G, stride = marks.numel() // n, self.plan_stride()
+        if plan is None:
+            plan = torch.empty((G, stride), dtype=torch.uint8, device=marks.device)
+        elif plan.numel() != G * stride:
+            raise QfecError(f"plan_build: plan has {plan.numel()} bytes for {G} groups of {stride}")
+        check(lib().qfec_plan_build(self._h, _dev_ptr(marks, what="marks"), G, int(mode), _dev_ptr(plan, what="plan"),
+                                    _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_plan_build")
+        return plan
+
+    def plan_apply(self, data, parity, plan, block_size=None, stream=None):
+        """Execute plans on a batch (qfec_plan_apply): data uint8 [G, k, pitch], parity uint8
+        [G, m, pitch], plan uint8 [G, plan_stride()] from plan_build, 16-byte aligned.  Reads no marks
+        and counts nothing; parity is written only where a plan lists parity rows."""
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch) or plan.numel() != G * self.plan_stride():
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
+                            f"plan {plan.numel()} for ({self.k},{self.m})")
+        block_size = pitch if block_size is None else block_size
+        check(lib().qfec_plan_apply(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                    _dev_ptr(plan, what="plan"), G, block_size, pitch, _stream_handle(stream)),
+              "qfec_plan_apply")
+
+    def _wide(self, name, data, parity, marks, block_size, failed, stream):
+        G, k, pitch = data.shape
+        if k != self.k or tuple(parity.shape) != (G, self.m, pitch) or marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"shape mismatch: data {tuple(data.shape)} parity {tuple(parity.shape)} "
+                            f"marks {marks.numel()} for ({self.k},{self.m})")
+        block_size = pitch if block_size is None else block_size
+        check(getattr(lib(), name)(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                   _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                   _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), name)
+
+    def reconstruct_wide(self, data, parity, marks, block_size=None, failed=None, stream=None):
+        """reconstruct for any k + m, asynchronous (qfec_reconstruct_wide): the decode plans are built
+        on the device from the marks.  Arguments as for reconstruct."""
+        self._wide("qfec_reconstruct_wide", data, parity, marks, block_size, failed, stream)
+
+    def repair_wide(self, data, parity, marks, block_size=None, failed=None, stream=None):
+        """repair for any k + m, asynchronous (qfec_repair_wide).  Arguments as for repair."""
+        self._wide("qfec_repair_wide", data, parity, marks, block_size, failed, stream)
+
+    def plan_host(self, marks_n, mode):
+        """The plan of one group-order mark vector over all n shards, computed on the CPU
+        (qfec_plan_build_host): uint8 [plan_stride()] in the layout of include/qfec.h."""
+        marks_n = np.ascontiguousarray(marks_n, dtype=np.uint8)
+        if marks_n.size != self.k + self.m:
+            raise QfecError(f"plan_host: {marks_n.size} marks for ({self.k},{self.m})")
+        out = np.zeros(self.plan_stride(), dtype=np.uint8)
+        check(lib().qfec_plan_build_host(self._h, marks_n.ctypes.data, int(mode), out.ctypes.data), "qfec_plan_build_host")
+        return out
+
     def locate(self, data, parity, block_size=None, culprit=None, marks=None, counts=None, stream=None):
         """Which single shard of each group is corrupted (qfec_locate)?  Returns culprit, a device
         int32 [G] tensor (allocated when not given): the shard id 0..k+m-1, or QFEC_LOC_CLEAN (-1),

@@ -280,6 +280,38 @@ struct LocErasedFinishArgs {
     int scrub;                     // 1: MULTI / AMBIGUOUS groups get all-zero marks_out (qfec_repair leaves them alone)
 };
 
+// device-built decode plans (qfec_plan.hip; layout and arithmetic in qfec_plan.hpp): one wave per
+// group turns the group's marks into its plan, for any k + m
+struct PlanBuildArgs {
+    const uint8_t* dmarks;    // [groups][k] data marks of this launch's groups
+    const uint8_t* pmarks;    // [groups][m] parity marks of this launch's groups
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] the encode's tables: dword 7 is the coefficient itself
+    const uint8_t* gf;        // exp[512] | log[256] (DevCtx::d_gf), staged into LDS
+    uint8_t* plan;            // [groups][stride] of this launch
+    unsigned int* failed;     // counter of groups whose plan has status 2; may be NULL
+    uint64_t groups;          // one 64-thread block each (< 2^31)
+    uint32_t stride;          // PlanLayout::stride
+    uint32_t lds;             // dynamic LDS bytes per block: QFEC_PLAN_GF_BYTES + plan_work_bytes(k, m)
+    int k, m;
+    int mode;                 // QFEC_PLAN_RECONSTRUCT / QFEC_PLAN_REPAIR
+    int quirk;                // the code's rs_stale_quirk
+};
+
+// a wave per (group, 64 columns) applies the group's plan: the k survivors in, the t listed rows out
+struct PlanApplyArgs {
+    uint8_t* data;            // [groups][k][pitch]
+    uint8_t* parity;          // [groups][m][pitch]; written only where a plan lists parity rows
+    const uint8_t* plan;      // [groups][stride] of this launch
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    uint64_t groups;
+    uint64_t pitch;
+    uint64_t dgs, pgs;        // bytes between groups: data rows, parity rows
+    uint32_t stride;          // PlanLayout::stride
+    uint32_t cols, wpg;       // lanes per row: 16-B columns (vec16) or bytes; waves per group at 64 of them
+    int k, m;
+    int vec16;
+};
+
 // FEC datagram batches (qfec_wire.hip): shards[G][n][pitch], wire[G][n][wire_pitch]
 struct WireArgs {
     const uint8_t* payload;   // send: concatenated payloads (16 readable bytes past the last)
@@ -381,6 +413,8 @@ hipError_t launch_locate2_pairs(const Locate2Args& a, hipStream_t stream);
 hipError_t launch_locate2_finish(const Locate2FinishArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased(const LocErasedArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t stream);
+hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream);
+hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);

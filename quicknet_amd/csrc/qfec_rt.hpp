@@ -14,6 +14,8 @@
 //   qfec_locate2.cpp   qfec_locate2 (its acceptance check and pair constants), qfec_scrub2
 //   qfec_update.cpp    qfec_encode_update, qfec_update (incremental parity on the encode's tables)
 //   qfec_ptrs.cpp      qfec_encode_ptrs, qfec_reconstruct_ptrs (shards given as a device table of addresses)
+//   qfec_plan.cpp      qfec_plan_build / qfec_plan_apply, qfec_reconstruct_wide / qfec_repair_wide (decode plans
+//                      built on the device, any k + m), qfec_plan_build_host
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
@@ -235,6 +237,9 @@ struct qfec_code {
     int l2_rc = 0;
     std::string l2_error;
     std::vector<uint8_t> l2_checks;  // [pairs][m-2][m]: F_ab, pairs in the order (0,1), (0,2), .. (n-2,n-1)
+    // device plans (qfec_plan.cpp): is `full` empty or [I; rows]?  Judged once per version under mu
+    uint64_t plan_chk_version = ~0ull;
+    bool plan_chk_ok = false;
 };
 
 namespace qfec {
