@@ -506,6 +506,85 @@ int qfec_locate_erased_plan(const qfec_code *code, const unsigned char *marks_n,
                             unsigned char *rows_out /* (m-t)*k: A */,
                             unsigned char *ratios_out /* k*(m-t-1): A_x[i]/A_x0[i] at [i*(m-t-1)+(x-1)], nullable */);
 
+/* Device-built check plans: single-shard error location for ANY k + m, beside lost shards or not,
+ * asynchronously.  qfec_locate_erased takes K, R, A and the ratios of a group from one host-built record
+ * per mask behind a 2^(k+m)-entry LUT (k + m <= 24) and keeps a candidate bit per shard in a 32-bit
+ * word (k, m <= 32).  Here the check plan of every group is computed on the device from the group's
+ * marks, on the caller's stream: no LUT, no qfec_prepare_*, no read-back, no host synchronisation, no
+ * limit on k, m or k + m.
+ *   Semantics: exactly qfec_locate_erased's, above -- K, R, A_x, the syndromes as true GF products, a
+ *     candidate only if its relation holds in EVERY byte of [0, block_size), and its table of verdicts
+ *     (LOST, UNCHECKED, CLEAN, a shard id, MULTI, AMBIGUOUS).  Marked shards are never read, bytes in
+ *     [block_size, pitch) never count, d_data / d_parity are never written by the locate.  With two
+ *     spares the verdict for two corrupted survivors is undefined, as there.
+ *   Codes: that every punctured code is MDS cannot be checked by enumerating masks at these widths, so
+ *     the calls accept exactly the codes whose parity rows are, byte for byte, what
+ *     qfec_code_new(QFEC_CAUCHY, k, m) or qfec_code_new(QFEC_VANDERMONDE, k, m) produces: those codes,
+ *     qfec_code_from_rows with those rows, and fec_new / reed_solomon_new handles that have not been
+ *     edited.  They are MDS: every entry of every A is non-zero, the ratios A_x1[i] / A_x0[i] are distinct
+ *     over i, a non-zero syndrome byte has at most one explanation when there are two spares or more,
+ *     and AMBIGUOUS occurs only with one spare.  Everything else is QFEC_EUNSUP with the cause in
+ *     qfec_last_error, m < 2 included (as qfec_locate); judged on the host once per version of the
+ *     code, before a device is touched, also with zero groups and null buffers.  Narrow codes are
+ *     accepted too; for them qfec_locate / qfec_locate_erased, with their compiled instances, are the
+ *     faster calls.
+ *   The check plan of a group, qfec_check_stride(code) bytes, public and fixed:
+ *       [0]   u16 S (spares: m - t, 0 when t >= m), u16 t (marked shards), u8 status (0 t = m: nothing
+ *             to check, 1 work, 2 t > m or a zero pivot, which accepted codes never have), pad to 16 bytes
+ *       [16]  32 bytes: the group's marks as one bit per shard id, four little-endian u64 words; set
+ *             for every status, so qfec_check_apply never needs the marks buffer
+ *       [48]  k survivor ids (K, u8), then m spare ids (u8, the first S valid, ascending), padded to 16
+ *       then  m x k bytes, the first S x k valid: A, row x over K in the order listed; padded to 16
+ *       then  k x (m - 1) bytes, the first k x (S - 1) valid: A_x[i] / A_x0[i] at [i*(S-1) + (x-1)],
+ *             x0 the first spare -- exactly qfec_locate_erased_plan's ratios_out; padded to 16
+ *       every unused byte is zero.  With status 0 or 2 only the header and the marks are set.
+ *   qfec_check_build writes the check plans of `groups` groups; d_marks is in the rs.c layout (non-zero
+ *     = lost) and may be NULL: no shard of any group is marked.  qfec_check_apply runs them on a batch:
+ *     d_culprit, d_marks_out (rs.c layout, may be NULL) and d_counts ([5], may be NULL; accumulated) as
+ *     in qfec_locate_erased.  It reads only the plan, never the marks, so one plan serves every scrub
+ *     pass while the same shards stay lost.  A buffer that qfec_check_build did not write is not a
+ *     check plan, and applying it is undefined.
+ *   d_check must be 16-byte aligned (the stride is a multiple of 16): plans are written 16 bytes at a
+ *     time and read as dwords.  A misaligned d_check is refused with QFEC_EINVAL, like d_plan.
+ *   qfec_locate_wide is qfec_check_build into stream-ordered scratch followed by qfec_check_apply, the
+ *     batch cut so that one chunk's plans stay under 64 MiB; d_marks may be NULL (complete groups) and
+ *     d_marks_out may be d_marks itself.
+ *   qfec_scrub_wide is qfec_locate_wide into stream-ordered scratch marks followed by qfec_repair_wide
+ *     with them, under qfec_scrub_erased's rules: a located culprit and the lost shards of its group are
+ *     rewritten to the original bytes in [0, block_size); the marks of MULTI and AMBIGUOUS groups are
+ *     zeroed, so nothing in those groups is rebuilt; LOST groups are untouched and counted into
+ *     *d_failed (may be NULL) by the repair; UNCHECKED groups, and CLEAN groups with losses, are
+ *     repaired as qfec_repair_wide repairs them.
+ *   16-byte lanes when both bases and the pitch allow, else byte by byte; batches beyond the 32-bit
+ *     index space of a launch are cut into several launches by the host.  The per-group working words
+ *     come from stream-ordered scratch.  A consistent batch costs one read of the k + m - t unmarked
+ *     rows of every group, plus the plans.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in qfec_last_error:
+ *     a null code, groups < 0, block_size < 1, pitch < block_size, a null required buffer with
+ *     groups > 0, a d_check that is not 16-byte aligned.  groups == 0 returns QFEC_OK and launches
+ *     nothing. */
+long long qfec_check_stride(const qfec_code *code);         /* bytes per group, a multiple of 16 */
+int qfec_check_build(qfec_code *code, const unsigned char *d_marks /* rs.c layout, NULL = no shard marked */,
+                     long long groups, unsigned char *d_check /* [groups][stride] */, void *stream);
+int qfec_check_apply(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                     const unsigned char *d_check, long long groups, int block_size, long long pitch,
+                     int *d_culprit            /* [groups] */,
+                     unsigned char *d_marks_out /* rs.c layout, nullable */,
+                     unsigned int *d_counts    /* [5] as qfec_locate_erased, nullable */, void *stream);
+int qfec_locate_wide(qfec_code *code, const unsigned char *d_data, const unsigned char *d_parity,
+                     const unsigned char *d_marks /* nullable: complete groups */, long long groups,
+                     int block_size, long long pitch, int *d_culprit /* [groups] */,
+                     unsigned char *d_marks_out /* nullable, may equal d_marks */,
+                     unsigned int *d_counts /* [5], nullable */, void *stream);
+int qfec_scrub_wide(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
+                    const unsigned char *d_marks /* nullable */, long long groups, int block_size,
+                    long long pitch, int *d_culprit /* nullable */, unsigned int *d_counts /* [5], nullable */,
+                    unsigned int *d_failed /* qfec_repair_wide's counter, nullable */, void *stream);
+/* The check plan of one group (group-order marks[n]) in the same layout, stride bytes.  Any k + m.
+ * CPU only, like qfec_plan_build_host; QFEC_EINVAL / QFEC_EUNSUP as above. */
+int qfec_check_build_host(const qfec_code *code, const unsigned char *marks_n,
+                          unsigned char *out_check /* stride bytes */);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

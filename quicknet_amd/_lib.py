@@ -21,6 +21,8 @@ EXPORTS = {
                "qfec_encode_update", "qfec_update", "qfec_encode_ptrs", "qfec_reconstruct_ptrs",
                "qfec_plan_stride", "qfec_plan_build", "qfec_plan_apply", "qfec_reconstruct_wide", "qfec_repair_wide",
                "qfec_plan_build_host",
+               "qfec_check_stride", "qfec_check_build", "qfec_check_apply", "qfec_locate_wide", "qfec_scrub_wide",
+               "qfec_check_build_host",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
                "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
@@ -96,6 +98,12 @@ def lib():
         "qfec_reconstruct_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_repair_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_plan_build_host": (i, [vp, vp, i, vp]),
+        "qfec_check_stride": (ll, [vp]),
+        "qfec_check_build": (i, [vp, vp, ll, vp, vp]),
+        "qfec_check_apply": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_locate_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_scrub_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
+        "qfec_check_build_host": (i, [vp, vp, vp]),
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),

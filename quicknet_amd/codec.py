@@ -586,6 +586,92 @@ class Code:
         return (s, surv, spares[:s].copy(), rows[:s * self.k].reshape(s, self.k).copy(),
                 ratios[:self.k * (s - 1)].reshape(self.k, s - 1).copy())
 
+    def check_stride(self):
+        """Bytes per group of a check plan (qfec_check_stride), a multiple of 16."""
+        n = lib().qfec_check_stride(self._h)
+        if n < 0:
+            check(int(n), "qfec_check_stride")
+        return int(n)
+
+    def check_build(self, marks=None, groups=None, check_plan=None, stream=None):
+        """The check plan of every group from its marks, on the device, for any k + m
+        (qfec_check_build).  marks: uint8 [G*k + G*m] (rs.c layout) on device, or None with
+        `groups` given: no shard of any group is marked.  Returns the plans, a device uint8
+        [G, check_stride()] tensor (allocated when not given; one passed in must start on a 16-byte
+        boundary: the call refuses it otherwise)."""
+        import torch
+        n = self.k + self.m
+        if marks is None:
+            if groups is None:
+                raise QfecError("check_build: groups is needed when no marks are given")
+            G = int(groups)
+        else:
+            if marks.numel() % n or (groups is not None and marks.numel() != int(groups) * n):
+                raise QfecError(f"check_build: {marks.numel()} marks are not groups * (k + m) = groups * {n}")
+            G = marks.numel() // n
+        stride = self.check_stride()
+        if check_plan is None:
+            check_plan = torch.empty((G, stride), dtype=torch.uint8, device="cuda" if marks is None else marks.device)
+        elif check_plan.numel() != G * stride:
+            raise QfecError(f"check_build: check_plan has {check_plan.numel()} bytes for {G} groups of {stride}")
+        check(lib().qfec_check_build(self._h, _dev_ptr(marks, what="marks"), G, _dev_ptr(check_plan, what="check_plan"),
+                                     _stream_handle(stream)), "qfec_check_build")
+        return check_plan
+
+    def check_host(self, marks_n):
+        """The check plan of one group-order mark vector over all n shards, computed on the CPU
+        (qfec_check_build_host): uint8 [check_stride()] in the layout of include/qfec.h."""
+        marks_n = np.ascontiguousarray(marks_n, dtype=np.uint8)
+        if marks_n.size != self.k + self.m:
+            raise QfecError(f"check_host: {marks_n.size} marks for ({self.k},{self.m})")
+        out = np.zeros(self.check_stride(), dtype=np.uint8)
+        check(lib().qfec_check_build_host(self._h, marks_n.ctypes.data, out.ctypes.data), "qfec_check_build_host")
+        return out
+
+    def check_apply(self, data, parity, check_plan, block_size=None, culprit=None, marks_out=None, counts=None,
+                    stream=None):
+        """Run check plans on a batch (qfec_check_apply): which single surviving shard of each group is
+        corrupted?  check_plan: uint8 [G, check_stride()] from check_build, 16-byte aligned; it holds
+        the marks, so no marks are read.  culprit, marks_out and counts as for locate_erased().
+        Returns culprit."""
+        G, block_size, pitch, culprit = self._group_args("check_apply", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=5)
+        if check_plan.numel() != G * self.check_stride():
+            raise QfecError(f"check_apply: check_plan has {check_plan.numel()} bytes for {G} groups of {self.check_stride()}")
+        if marks_out is not None and marks_out.numel() != G * (self.k + self.m):
+            raise QfecError(f"check_apply: marks_out has {marks_out.numel()} elements for {G} groups of {self.k + self.m}")
+        check(lib().qfec_check_apply(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                     _dev_ptr(check_plan, what="check_plan"), G, block_size, pitch,
+                                     _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks_out, what="marks_out"),
+                                     _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_check_apply")
+        return culprit
+
+    def locate_wide(self, data, parity, marks=None, block_size=None, culprit=None, marks_out=None, counts=None,
+                    stream=None):
+        """locate_erased() for any k + m, asynchronous (qfec_locate_wide): the check plans are built on
+        the device from the marks.  marks may be None (complete groups); the other arguments and the
+        result as for locate_erased().  Accepts the codes qfec_code_new generates."""
+        G, block_size, pitch, culprit = self._group_args("locate_wide", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=5, marks=marks)
+        if marks_out is not None and marks_out.numel() != G * (self.k + self.m):
+            raise QfecError(f"locate_wide: marks_out has {marks_out.numel()} elements for {G} groups of {self.k + self.m}")
+        check(lib().qfec_locate_wide(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                     _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                     _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks_out, what="marks_out"),
+                                     _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate_wide")
+        return culprit
+
+    def scrub_wide(self, data, parity, marks=None, block_size=None, culprit=None, counts=None, failed=None, stream=None):
+        """locate_wide() + repair_wide() in one call (qfec_scrub_wide), under scrub_erased()'s rules,
+        for any k + m.  Returns culprit as locate_erased() does."""
+        G, block_size, pitch, culprit = self._group_args("scrub_wide", data, parity, block_size, culprit, counts=counts,
+                                                         ncounts=5, marks=marks)
+        check(lib().qfec_scrub_wide(self._h, _dev_ptr(data, what="data"), _dev_ptr(parity, what="parity"),
+                                    _dev_ptr(marks, what="marks"), G, block_size, pitch,
+                                    _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                                    _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_scrub_wide")
+        return culprit
+
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15
     def pack_datagrams(self, payload, offsets, sizes, seq, checksum=True, shard_pitch=None, wire_pitch=None,
                        stream=None):

@@ -1,0 +1,314 @@
+// qfec_check.hip -- single-shard error location at any k + m, beside lost shards or not
+// (qfec_check_build / qfec_check_apply of include/qfec.h, and qfec_locate_wide / qfec_scrub_wide on
+// top of them).  The semantics are qfec_locate_erased's; where that call takes a group's constants
+// from a host-built record per mask behind a 2^(k+m)-entry LUT, here the check plan of every group is
+// computed on the device from the group's marks.
+//
+// k_check_build: k_plan_build's frame, one wave (a 64-thread block) per group: the marks in four
+// ballot passes (or none marked), the GF tables staged in LDS, then check_group of qfec_plan.hpp, the
+// text the host query qfec_check_build_host runs.
+//
+// k_check_apply: k_plan_apply's mapping, a wave per (group, 64 columns).  Status, S, ids and
+// coefficients are wave-uniform and come through scalar loads of the plan.  The wave loops over the
+// k survivors and accumulates the syndromes of up to CCH spares per pass; the first spare's syndrome
+// is kept across passes.  A wave whose syndromes are all zero ends there.
+//
+// Cold path.  For the accepted codes (MDS) a non-zero syndrome byte has at most one explanation, so
+// the wave derives ONE candidate from one byte and verifies it against every lane's bytes, instead of
+// keeping a candidate bit per shard (qfec_locate_erased's 32-bit words do not reach k = 254).  Per
+// pass: the first lane with a non-zero byte gives that byte's syndromes z_0 (first spare) and z_x
+// (the pass's spares).  z_0 = 0 and exactly one z_y != 0: spare y.  z_0 != 0 and every z_x = 0: the
+// first spare.  Otherwise the position c of K with ratio[c][x1] . z_0 = z_x1, x1 the pass's first
+// spare after x0: the lanes test c = lane, lane + 64, .. and one ballot picks c.  Every lane then
+// tests the wave-uniform candidate on its own bytes, and lane 0 folds the result into the group's
+// three words: min and max of the candidate shard id, and flags (1 some byte non-zero, 2 some byte
+// unexplained).  One candidate over every wave and pass and no unexplained byte is exactly "this
+// shard's relation holds in every byte, and no other's does".  With one spare only the flag is set.
+// k_check_finish turns the words and the plan's head into verdicts, marks and counts.
+#include "../../include/qfec.h"
+#include "qfec_device.hpp"
+#include "qfec_plan.hpp"
+
+namespace qfec {
+
+constexpr int CCH = 8;  // spares per pass of k_check_apply
+
+__global__ void __launch_bounds__(64) k_check_build(PlanBuildArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];  // [exp 512 | log 256][check_work_bytes]
+    const int lane = threadIdx.x;
+    const uint64_t g = blockIdx.x;
+    if (g >= a.groups) return;
+    const int k = a.k, m = a.m, n = k + m;
+    for (int i = lane; i < QFEC_PLAN_GF_BYTES / 4; i += 64)
+        reinterpret_cast<uint32_t*>(lds)[i] = reinterpret_cast<const uint32_t*>(a.gf)[i];
+    uint64_t mk[4] = {0, 0, 0, 0};
+    if (a.dmarks) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int i = p * 64 + lane;
+            uint32_t v = 0;
+            if (i < k) v = a.dmarks[g * (uint64_t)k + i];
+            else if (i < n) v = a.pmarks[g * (uint64_t)m + (i - k)];
+            mk[p] = __ballot(v != 0);
+        }
+    }
+    __syncthreads();
+    const PlanCode C{reinterpret_cast<const uint8_t*>(a.tab + 7), QFEC_TAB_STRIDE * 4, k, m, 0, lds, lds + 512};
+    (void)check_group(C, mk, lds + QFEC_PLAN_GF_BYTES, a.plan + g * a.stride, PlanWaveLanes{lane});
+}
+
+// byte idx of the plan through a scalar dword load
+__device__ __forceinline__ uint32_t check_u8(cptr32 pw, int idx) { return (pw[idx >> 2] >> ((idx & 3) * 8)) & 0xFFu; }
+
+template <int D>
+__device__ __forceinline__ void check_ld(uint32_t (&v)[D], const uint8_t* p) {
+    if constexpr (D == 4) ldv<4>(v, p);
+    else v[0] = *p;
+}
+
+// byte b of lane src's v, wave-uniform
+template <int D>
+__device__ __forceinline__ uint32_t check_byte_at(const uint32_t (&v)[D], int b, int src) {
+    uint32_t w = v[0];
+    if constexpr (D == 4) {
+        const int d = b >> 2;
+        w = d == 0 ? v[0] : d == 1 ? v[1] : d == 2 ? v[2] : v[3];
+    }
+    return ((uint32_t)__builtin_amdgcn_readlane((int)w, src) >> ((b & 3) * 8)) & 0xFFu;
+}
+
+// D = 4: 16-byte columns; D = 1: one byte per lane, in the low byte of a dword
+template <int D>
+__global__ void __launch_bounds__(256) k_check_apply(CheckApplyArgs a, const uint8_t* __restrict__ check) {
+    static_assert(D == 4 || D == 1, "16-B columns or bytes");
+    const int lane = threadIdx.x & 63;
+    const uint32_t wid = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t g = wid / a.wpg;
+    const uint32_t part = wid - g * a.wpg;
+    if (g >= a.groups) return;
+    const int k = a.k, m = a.m, n = k + m;
+    const CheckLayout CL = check_layout(k, m);
+    const uint8_t* chk = check + (uint64_t)g * a.stride;
+    const cptr32 pw = (cptr32)chk;
+    const cptr32 t256 = (cptr32)a.t256;
+    const int S = (int)(pw[0] & 0xFFFFu);
+    if ((pw[1] & 0xFFu) != (uint32_t)QFEC_PLAN_WORK || S < 1 || S > m) return;
+    // the lanes past the row's last column stay for the ballots: they read column 0 and count no byte
+    const uint32_t col = part * 64u + lane;
+    const bool live = col < a.cols;
+    const uint64_t off = live ? (uint64_t)col * (D == 4 ? 16u : 1u) : 0u;
+    uint32_t mk[D];
+    if constexpr (D == 4) {
+        const uint4 q = column_mask(a.block, live ? col : 0u);
+        mk[0] = live ? q.x : 0u; mk[1] = live ? q.y : 0u; mk[2] = live ? q.z : 0u; mk[3] = live ? q.w : 0u;
+    } else {
+        mk[0] = live ? 0xFFu : 0u;
+    }
+    const uint8_t* data_g = a.data + (uint64_t)g * a.dgs;
+    const uint8_t* par_g = a.parity + (uint64_t)g * a.pgs;
+    auto row = [&](uint32_t s) -> const uint8_t* {
+        return s < (uint32_t)k ? data_g + (uint64_t)s * a.pitch : par_g + (uint64_t)(s - k) * a.pitch;
+    };
+
+    uint32_t s0[D];  // the first spare's syndrome, from pass 0
+#pragma unroll
+    for (int d = 0; d < D; ++d) s0[d] = 0;
+    for (int x0 = 0; x0 < S; x0 += CCH) {
+        uint32_t acc[CCH][D];
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc[j][d] = 0;
+        for (int c = 0; c < k; ++c) {
+            const uint32_t s = check_u8(pw, QFEC_CHECK_IDS + c);
+            if (s >= (uint32_t)n) return;  // not a check plan of this code
+            uint32_t v[D];
+            check_ld<D>(v, row(s) + off);
+            Sel sl[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) sl[d] = gf_sel(v[d]);
+#pragma unroll
+            for (int j = 0; j < CCH; ++j)
+                if (x0 + j < S) {
+                    const cptr32 tc = t256 + check_u8(pw, CL.a_off + (x0 + j) * k + c) * QFEC_TAB_STRIDE;
+                    const uint32_t t0 = tc[0], t1 = tc[1], t2 = tc[2], t3 = tc[3], t4 = tc[4];
+#pragma unroll
+                    for (int d = 0; d < D; ++d)
+                        acc[j][d] = xor3(acc[j][d], pp0(sl[d], t0, t1), pp1(sl[d], t2, t3)) ^ pp2(sl[d], t4);
+                }
+        }
+        uint32_t nz[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) nz[d] = 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (x0 + j < S) {
+                const uint32_t sp = check_u8(pw, QFEC_CHECK_IDS + k + x0 + j);
+                if (sp >= (uint32_t)n) return;
+                uint32_t p[D];
+                check_ld<D>(p, row(sp) + off);
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    acc[j][d] = (acc[j][d] ^ p[d]) & mk[d];  // bytes >= block_size never count
+                    nz[d] |= acc[j][d];
+                }
+            }
+        if (x0 == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) s0[d] = acc[0][d];
+        }
+        uint32_t any = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            nz[d] |= s0[d];
+            any |= nz[d];
+        }
+        const uint64_t hot = __ballot(any != 0);
+        if (!hot) continue;  // consistent so far: the common case ends with the loop
+
+        // ---- cold: one candidate from one byte, then every lane's bytes against it
+        if (S == 1) {  // no ratio to test: the finish kernel calls the group AMBIGUOUS
+            if (lane == 0) atomicOr(a.flags + g, 1u);
+            continue;
+        }
+        const int src = __builtin_ctzll(hot);
+        int bsel = 0;
+#pragma unroll
+        for (int d = D - 1; d >= 0; --d)
+            if (nz[d]) bsel = d * 4 + (__builtin_ctz(nz[d]) >> 3);
+        const int b = __builtin_amdgcn_readlane(bsel, src);
+        const uint32_t z0 = check_byte_at<D>(s0, b, src);
+        const int jlo = x0 == 0 ? 1 : 0;  // acc[0] of pass 0 is s0 itself
+        int cnt = 0, first = -1;
+        uint32_t z1 = 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (j >= jlo && x0 + j < S) {
+                const uint32_t zj = check_byte_at<D>(acc[j], b, src);
+                if (j == jlo) z1 = zj;
+                if (zj) {
+                    if (!cnt) first = j;
+                    ++cnt;
+                }
+            }
+        enum { NONE = 0, KPOS, SPARE, SPARE0 };
+        int kind = NONE, cpos = 0;
+        if (z0 == 0) {
+            kind = cnt == 1 ? SPARE : NONE;
+        } else if (cnt == 0) {
+            kind = SPARE0;
+        } else {
+            // the position c of K with ratio[c][x1] . z0 = z1: each lane multiplies its ratio by the
+            // wave-uniform z0 through z0's perm table
+            const cptr32 tz = t256 + z0 * QFEC_TAB_STRIDE;
+            const uint32_t t0 = tz[0], t1 = tz[1], t2 = tz[2], t3 = tz[3], t4 = tz[4];
+            const int x1 = x0 + jlo;
+            for (int c0 = 0; c0 < k; c0 += 64) {
+                const int c = c0 + lane;
+                bool hit = false;
+                if (c < k) {
+                    const uint32_t r = chk[CL.r_off + c * (S - 1) + (x1 - 1)];
+                    hit = (gf_mul4(gf_sel(r), t0, t1, t2, t3, t4) & 0xFFu) == z1;
+                }
+                const uint64_t hits = __ballot(hit);
+                if (hits) {
+                    kind = KPOS;
+                    cpos = c0 + __builtin_ctzll(hits);
+                    break;
+                }
+            }
+        }
+        bool ok = kind != NONE;
+        if (kind == SPARE)
+#pragma unroll
+            for (int d = 0; d < D; ++d) ok = ok && s0[d] == 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (j >= jlo && x0 + j < S) {
+                if (kind == KPOS) {
+                    const cptr32 tc = t256 + check_u8(pw, CL.r_off + cpos * (S - 1) + (x0 + j - 1)) * QFEC_TAB_STRIDE;
+                    const uint32_t t0 = tc[0], t1 = tc[1], t2 = tc[2], t3 = tc[3], t4 = tc[4];
+#pragma unroll
+                    for (int d = 0; d < D; ++d) ok = ok && gf_mul4(gf_sel(s0[d]), t0, t1, t2, t3, t4) == acc[j][d];
+                } else if (kind == SPARE0 || j != first) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) ok = ok && acc[j][d] == 0;
+                }
+            }
+        const bool all_ok = kind != NONE && __ballot(!ok) == 0;
+        if (lane == 0) {
+            atomicOr(a.flags + g, all_ok ? 1u : 3u);
+            if (all_ok) {
+                const uint32_t id = kind == KPOS    ? check_u8(pw, QFEC_CHECK_IDS + cpos)
+                                    : kind == SPARE ? check_u8(pw, QFEC_CHECK_IDS + k + x0 + first)
+                                                    : check_u8(pw, QFEC_CHECK_IDS + k);
+                atomicMin(a.cmin + g, id);
+                atomicMax(a.cmax + g, id);
+            }
+        }
+    }
+}
+
+// one lane per group
+__global__ void __launch_bounds__(256) k_check_finish(CheckFinishArgs a) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    int verdict = -1;  // also for lanes past the last group
+    if (g < a.groups) {
+        const uint32_t* pw = reinterpret_cast<const uint32_t*>(a.check + g * a.stride);
+        const int S = (int)(pw[0] & 0xFFFFu);
+        const uint32_t status = pw[1] & 0xFFu;
+        uint64_t mk[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) mk[w] = pw[4 + 2 * w] | (uint64_t)pw[5 + 2 * w] << 32;
+        int id = QFEC_LOC_CLEAN;
+        if (status == (uint32_t)QFEC_PLAN_FAILED) {
+            id = QFEC_LOC_LOST;
+        } else if (status == (uint32_t)QFEC_PLAN_NONE) {
+            id = QFEC_LOC_UNCHECKED;
+        } else if (a.flags[g] != 0) {
+            if (S == 1) id = QFEC_LOC_AMBIGUOUS;
+            else if ((a.flags[g] & 2u) || a.cmin[g] != a.cmax[g]) id = QFEC_LOC_MULTI;
+            else id = (int)a.cmin[g];
+        }
+        if (a.culprit) a.culprit[g] = id;
+        if (a.marks_out) {
+            // the input marks as 0 / 1, plus the culprit; for the scrub nothing in a group that must
+            // stay as it is.  This lane alone touches the group's bytes, and the input marks are in the plan
+            const bool none = a.scrub && (id == QFEC_LOC_MULTI || id == QFEC_LOC_AMBIGUOUS);
+            const int k = a.k, m = a.m;
+            uint8_t* dm = a.marks_out + (a.g0 + g) * (uint64_t)k;
+            uint8_t* pm = a.marks_out + a.all_groups * (uint64_t)k + (a.g0 + g) * (uint64_t)m;
+            for (int i = 0; i < k; ++i) dm[i] = none ? 0 : (uint8_t)(plan_bit(mk, i) | (i == id));
+            for (int j = 0; j < m; ++j) pm[j] = none ? 0 : (uint8_t)(plan_bit(mk, k + j) | (k + j == id));
+        }
+        verdict = id >= 0 ? 0 : id == QFEC_LOC_CLEAN ? -1 : -id - 1;  // MULTI -2 -> 1 ... LOST -5 -> 4
+    }
+    if (a.counts) block_counts<5>(verdict, a.counts);  // uniform over the grid
+}
+
+hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    if (a.groups > 0x7FFFFFFFull / 64u || a.lds > 65536u) return hipErrorInvalidValue;  // caller chunks
+    hipLaunchKernelGGL(k_check_build, dim3((unsigned)a.groups), dim3(64), a.lds, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream) {
+    if (a.groups == 0 || a.cols == 0) return hipSuccess;
+    const uint64_t waves = a.groups * (uint64_t)a.wpg;
+    if (a.wpg == 0 || waves * 64u > 0x7FFFFFFFull || !a.flags || !a.cmin || !a.cmax) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (a.vec16) hipLaunchKernelGGL((k_check_apply<4>), dim3(grid), dim3(256), 0, stream, a, a.check);
+    else hipLaunchKernelGGL((k_check_apply<1>), dim3(grid), dim3(256), 0, stream, a, a.check);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    if (!a.check || !a.flags || !a.cmin || !a.cmax || a.groups > 0x7FFFFFFFull * 256u) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((a.groups + 255) / 256);
+    hipLaunchKernelGGL(k_check_finish, dim3(grid), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace qfec

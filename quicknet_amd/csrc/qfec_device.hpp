@@ -152,6 +152,19 @@ __device__ __forceinline__ uint64_t fast_div(uint64_t n, const DivMagic& d) {
     return d.pow2 ? (n >> d.shift) : ((n * d.mul) >> (32 + d.shift));
 }
 
+// ------------------------------------------------------------------ the lanes of qfec_plan.hpp on the device
+// plan_group / check_group run by one wave that is its whole block (k_plan_build, k_check_build); the
+// host's counterpart is PlanHostLanes
+struct PlanWaveLanes {
+    static constexpr int n = 64;
+    int lane;
+    __device__ __forceinline__ void sync() const { __syncthreads(); }  // the block is this one wave
+    __device__ __forceinline__ int uni(int x) const { return __builtin_amdgcn_readfirstlane(x); }
+    __device__ __forceinline__ void store16(uint8_t* dst, const uint32_t (&w)[4]) const {
+        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+
 // ------------------------------------------------------------------ compact records
 // where a decode record's coefficient tables are: in the 256-entry table of every coefficient
 // value, at the byte offsets the record's header lists (RecordLayout::coff).  Reading only the

@@ -312,6 +312,46 @@ struct PlanApplyArgs {
     int vec16;
 };
 
+// device-built check plans (qfec_check.hip; layout and arithmetic in qfec_plan.hpp): single-shard
+// error location at any k + m.  k_check_build takes a PlanBuildArgs (dmarks NULL: nothing marked;
+// mode, quirk and failed unused; lds = QFEC_PLAN_GF_BYTES + check_work_bytes(k, m)).
+// A wave per (group, 64 columns) forms the group's syndromes from its check plan and folds what it
+// finds into the group's three words
+struct CheckApplyArgs {
+    const uint8_t* data;      // [groups][k][pitch]
+    const uint8_t* parity;    // [groups][m][pitch]
+    const uint8_t* check;     // [groups][stride] of this launch
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    unsigned int* flags;      // [groups] of this launch, zero before it: 1 a non-zero syndrome byte, 2 one that no
+                              // single shard explains
+    unsigned int* cmin;       // [groups], all ones before it: the lowest candidate shard id of any wave
+    unsigned int* cmax;       // [groups], zero before it: the highest
+    uint64_t groups;
+    uint64_t pitch;
+    uint64_t dgs, pgs;        // bytes between groups: data rows, parity rows
+    uint32_t stride;          // CheckLayout::stride
+    uint32_t cols, wpg;       // lanes per row: 16-B columns (vec16) or bytes; waves per group at 64 of them
+    uint32_t block;           // block_size: bytes of a row that count
+    int k, m;
+    int vec16;
+};
+
+// the verdict per group from its check plan's head and its three words
+struct CheckFinishArgs {
+    const uint8_t* check;          // [groups][stride] of this launch
+    const unsigned int* flags;     // [groups] of this launch
+    const unsigned int* cmin;
+    const unsigned int* cmax;
+    int* culprit;                  // [groups] of this launch: shard id or QFEC_LOC_*; may be NULL
+    uint8_t* marks_out;            // rs.c layout over all_groups; may be NULL
+    unsigned int* counts;          // [5] located, multi, ambiguous, unchecked, lost; may be NULL
+    uint64_t groups;               // of this launch
+    uint64_t g0, all_groups;       // where this launch's groups sit in marks_out
+    uint32_t stride;
+    int k, m;
+    int scrub;                     // 1: MULTI / AMBIGUOUS groups get all-zero marks_out (the repair leaves them alone)
+};
+
 // FEC datagram batches (qfec_wire.hip): shards[G][n][pitch], wire[G][n][wire_pitch]
 struct WireArgs {
     const uint8_t* payload;   // send: concatenated payloads (16 readable bytes past the last)
@@ -415,6 +455,9 @@ hipError_t launch_locate_erased(const LocErasedArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t stream);
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream);
+hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream);
+hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream);
+hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);

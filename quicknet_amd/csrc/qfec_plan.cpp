@@ -14,7 +14,7 @@ constexpr long long kPlanScratchCap = 64ll << 20;
 
 // rs.c's decode with a partially inverted matrix is not reproduced here: a code that carries an
 // rs.c decode matrix must have it equal to [I; rows].  Judged once per code version.
-static int plan_code_check(const qfec_code* cc, const char* who) {
+int plan_code_check(const qfec_code* cc, const char* who) {
     qfec_code* c = const_cast<qfec_code*>(cc);
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->plan_chk_version != c->version) {
@@ -33,7 +33,7 @@ static int plan_code_check(const qfec_code* cc, const char* who) {
     return QFEC_EUNSUP;
 }
 
-static const char* bad_rows_args(const qfec_code* code, long long groups, int block_size, long long pitch) {
+const char* bad_rows_args(const qfec_code* code, long long groups, int block_size, long long pitch) {
     return !code              ? "null code"
            : groups < 0       ? "groups < 0"
            : block_size < 1   ? "block_size < 1"
@@ -42,9 +42,9 @@ static const char* bad_rows_args(const qfec_code* code, long long groups, int bl
 }
 
 // the build kernel stores a plan 16 bytes at a time and the apply kernel reads it as dwords
-static bool plan_misaligned(const void* d_plan) { return ((uintptr_t)d_plan & 15) != 0; }
+bool plan_misaligned(const void* d_plan) { return ((uintptr_t)d_plan & 15) != 0; }
 
-static int refuse(const char* who, const char* why) {
+int refuse(const char* who, const char* why) {
     set_error("%s: invalid argument (%s)", who, why);
     return QFEC_EINVAL;
 }

@@ -19,16 +19,6 @@ namespace qfec {
 
 constexpr int PCH = 8;  // output rows per pass of k_plan_apply
 
-struct PlanWaveLanes {
-    static constexpr int n = 64;
-    int lane;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }  // the block is this one wave
-    __device__ __forceinline__ int uni(int x) const { return __builtin_amdgcn_readfirstlane(x); }
-    __device__ __forceinline__ void store16(uint8_t* dst, const uint32_t (&w)[4]) const {
-        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
-
 __global__ void __launch_bounds__(64) k_plan_build(PlanBuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];  // [exp 512 | log 256][plan_work_bytes]
     const int lane = threadIdx.x;

@@ -106,6 +106,69 @@ QFEC_HD uint8_t plan_coef(const PlanCode& C, const PlanLayout& PL, const uint8_t
     return acc;
 }
 
+// Minv of M = P[Q][E] (e x e) into the right half of A (e x 2e): Gauss-Jordan on [M | I], from the
+// ids in hdr (the last e survivors are Q, the first e lost ids E).  colv: e bytes.  False for a
+// singular M.  Every lane of L calls it.
+template <class Lanes>
+QFEC_HD bool plan_invert(const PlanCode& C, const PlanLayout& PL, const uint8_t* hdr, int e, uint8_t* colv, uint8_t* A,
+                         const Lanes& L) {
+    const int k = C.k;
+    const int w = 2 * e;
+    for (int idx = L.lane; idx < e * w; idx += L.n) {
+        const int r = idx / w, c = idx - r * w;
+        const int q = hdr[PL.surv_off + k - e + r] - k;
+        A[idx] = c < e ? C.P[(size_t)(q * k + hdr[PL.lost_off + c]) * C.pstride] : (uint8_t)(c - e == r);
+    }
+    L.sync();
+    // lanes across the 2e columns; any pivot order gives the same inverse
+    for (int c = 0; c < e; ++c) {
+        int p = c;
+        while (p < e && A[p * w + c] == 0) ++p;
+        p = L.uni(p);
+        if (p == e) return false;
+        const int ls = (255 - C.glog[A[p * w + c]]) % 255;  // log of the pivot's inverse
+        L.sync();
+        for (int j = L.lane; j < w; j += L.n) {
+            const uint8_t a = A[p * w + j], b = A[c * w + j];
+            A[c * w + j] = plan_mul_log(C, ls, a);
+            if (p != c) A[p * w + j] = b;
+        }
+        L.sync();
+        for (int r = L.lane; r < e; r += L.n) colv[r] = A[r * w + c];
+        L.sync();
+        for (int r = 0; r < e; ++r) {
+            const uint8_t q = colv[r];
+            if (r == c || !q) continue;
+            const int lq = C.glog[q];
+            for (int j = L.lane; j < w; j += L.n) A[r * w + j] ^= plan_mul_log(C, lq, A[c * w + j]);
+        }
+        L.sync();
+    }
+    return true;
+}
+
+// rows [j0, j1) of X (e bytes each) from the inverse plan_invert left in A: Minv's row for j < e, the
+// R row of the parity shard hdr lists as lost id j above that.  The caller syncs before X is read.
+template <class Lanes>
+QFEC_HD void plan_factors(const PlanCode& C, const PlanLayout& PL, const uint8_t* hdr, const uint8_t* A, uint8_t* X,
+                          int e, int j0, int j1, const Lanes& L) {
+    const int k = C.k;
+    const int w = 2 * e;
+    for (int idx = j0 * e + L.lane; idx < j1 * e; idx += L.n) {
+        const int j = idx / e, r = idx - j * e;
+        uint8_t x;
+        if (j < e) {
+            x = A[j * w + e + r];
+        } else {
+            const int pj = hdr[PL.lost_off + j] - k;
+            x = 0;
+            for (int jj = 0; jj < e; ++jj)
+                x ^= plan_mul(C, C.P[(size_t)(pj * k + hdr[PL.lost_off + jj]) * C.pstride], A[jj * w + e + r]);
+        }
+        X[idx] = x;
+    }
+}
+
 // The plan of one group into out[stride] (whole 16-byte stores, unused bytes zero).  Every lane of
 // L calls it with the same arguments; W = plan_work_bytes(k, m) bytes shared by the lanes.
 // mode 0: the erased data rows (qfec_reconstruct's rule), 1: every marked shard (qfec_repair's).
@@ -138,54 +201,9 @@ QFEC_HD int plan_group(const PlanCode& C, const uint64_t (&mk)[4], int mode, uin
             }
         }
         L.sync();
-        const int w = 2 * e;
-        for (int idx = L.lane; idx < e * w; idx += L.n) {
-            const int r = idx / w, c = idx - r * w;
-            const int q = hdr[PL.surv_off + k - e + r] - k;
-            A[idx] = c < e ? C.P[(size_t)(q * k + hdr[PL.lost_off + c]) * C.pstride] : (uint8_t)(c - e == r);
-        }
-        L.sync();
-        // Gauss-Jordan on [M | I], lanes across the 2e columns; any pivot order gives the same inverse
-        for (int c = 0; c < e; ++c) {
-            int p = c;
-            while (p < e && A[p * w + c] == 0) ++p;
-            p = L.uni(p);
-            if (p == e) {
-                status = QFEC_PLAN_FAILED;  // singular: explicit rows that are not MDS
-                break;
-            }
-            const int ls = (255 - C.glog[A[p * w + c]]) % 255;  // log of the pivot's inverse
-            L.sync();
-            for (int j = L.lane; j < w; j += L.n) {
-                const uint8_t a = A[p * w + j], b = A[c * w + j];
-                A[c * w + j] = plan_mul_log(C, ls, a);
-                if (p != c) A[p * w + j] = b;
-            }
-            L.sync();
-            for (int r = L.lane; r < e; r += L.n) colv[r] = A[r * w + c];
-            L.sync();
-            for (int r = 0; r < e; ++r) {
-                const uint8_t q = colv[r];
-                if (r == c || !q) continue;
-                const int lq = C.glog[q];
-                for (int j = L.lane; j < w; j += L.n) A[r * w + j] ^= plan_mul_log(C, lq, A[c * w + j]);
-            }
-            L.sync();
-        }
+        if (!plan_invert(C, PL, hdr, e, colv, A, L)) status = QFEC_PLAN_FAILED;  // singular: explicit rows that are not MDS
         if (status == QFEC_PLAN_WORK) {
-            for (int idx = L.lane; idx < t * e; idx += L.n) {
-                const int j = idx / e, r = idx - j * e;
-                uint8_t x;
-                if (j < e) {
-                    x = A[j * w + e + r];
-                } else {
-                    const int pj = hdr[PL.lost_off + j] - k;
-                    x = 0;
-                    for (int jj = 0; jj < e; ++jj)
-                        x ^= plan_mul(C, C.P[(size_t)(pj * k + hdr[PL.lost_off + jj]) * C.pstride], A[jj * w + e + r]);
-                }
-                X[idx] = x;
-            }
+            plan_factors(C, PL, hdr, A, X, e, 0, t, L);
             L.sync();
             // module/rs.c:116-117: a zero column-0 coefficient leaves the output's bytes in place (data rows only)
             if (C.quirk)
@@ -216,6 +234,123 @@ QFEC_HD int plan_group(const PlanCode& C, const uint64_t (&mk)[4], int mode, uin
             for (int q = 0; q < 16; ++q) {
                 if (i0 + q < ncoef) wd[q >> 2] |= (uint32_t)plan_coef(C, PL, hdr, X, e, j, c) << (8 * (q & 3));
                 if (++c == k) { c = 0; ++j; }
+            }
+        }
+        L.store16(out + pos, wd);
+    }
+    return status;
+}
+
+// ---------------------------------------------------------------- check plans (qfec_check_build)
+// What single-shard error location needs of one group (include/qfec.h, qfec_check_build): K, the
+// spares R, the rows A_x that predict each spare from K, and the ratios A_x[i] / A_x0[i].  A_x is the
+// row the repair plan above gives for x under the mask E + R (every shard outside K), so the
+// elimination and the row factors are plan_invert / plan_factors over the same ids: Q, the parity
+// rows inside K, and E's data ids are the same under either mask.
+constexpr int QFEC_CHECK_MARKS = 16;  // after the header [u16 S][u16 t][u8 status][pad]: 32 bytes of mark bits
+constexpr int QFEC_CHECK_IDS = 48;
+
+struct CheckLayout {
+    int a_off, r_off;  // m x k rows, k x (m - 1) ratios, each from a 16-byte boundary
+    int stride;        // bytes per group, a multiple of 16
+};
+
+QFEC_HD CheckLayout check_layout(int k, int m) {
+    CheckLayout L;
+    L.a_off = (QFEC_CHECK_IDS + k + m + 15) & ~15;
+    L.r_off = (L.a_off + m * k + 15) & ~15;
+    L.stride = (L.r_off + k * (m > 1 ? m - 1 : 0) + 15) & ~15;
+    return L;
+}
+
+// working memory of check_group: plan_group's, and the first spare's row (k bytes)
+QFEC_HD int check_work_bytes(int k, int m) { return plan_work_bytes(k, m) + k; }
+
+// The check plan of one group into out[stride] (whole 16-byte stores, unused bytes zero), called as
+// plan_group is; W = check_work_bytes(k, m).  Returns the status: 0 t = m, 1 work, 2 t > m or a
+// singular matrix over K.
+template <class Lanes>
+QFEC_HD int check_group(const PlanCode& C, const uint64_t (&mk)[4], uint8_t* W, uint8_t* out, const Lanes& L) {
+    const int k = C.k, m = C.m, n = k + m;
+    const PlanLayout PL = plan_layout(k, m);
+    const CheckLayout CL = check_layout(k, m);
+    const int em = k < m ? k : m;
+    uint8_t* hdr = W;  // ids as plan_group keeps them: K, then as "lost" E's data ids and the spares
+    uint8_t* row0 = W + PL.coef_off;
+    uint8_t* colv = row0 + k;
+    uint8_t* A = colv + em;
+    uint8_t* X = A + 2 * em * em;
+
+    const int e = plan_below(mk, k);
+    const int t = plan_below(mk, n);
+    const int S = t < m ? m - t : 0;
+    int status = t > m ? QFEC_PLAN_FAILED : t == m ? QFEC_PLAN_NONE : QFEC_PLAN_WORK;
+    if (status == QFEC_PLAN_WORK) {
+        for (int i = L.lane; i < n; i += L.n) {
+            const int below = plan_below(mk, i);
+            if (plan_bit(mk, i)) {
+                if (i < k) hdr[PL.lost_off + below] = (uint8_t)i;
+            } else if (i - below < k) {
+                hdr[PL.surv_off + i - below] = (uint8_t)i;
+            } else {
+                hdr[PL.lost_off + e + (i - below - k)] = (uint8_t)i;  // a spare: a parity row outside K
+            }
+        }
+        L.sync();
+        if (!plan_invert(C, PL, hdr, e, colv, A, L)) {
+            status = QFEC_PLAN_FAILED;
+        } else {
+            plan_factors(C, PL, hdr, A, X, e, e, e + S, L);
+            L.sync();
+            for (int i = L.lane; i < k; i += L.n) row0[i] = plan_coef(C, PL, hdr, X, e, e, i);
+        }
+        L.sync();
+    }
+    const int nids = status == QFEC_PLAN_WORK ? k + S : 0;
+    const int na = status == QFEC_PLAN_WORK ? S * k : 0;
+    const int nr = status == QFEC_PLAN_WORK ? k * (S - 1) : 0;
+    for (int pos = L.lane * 16; pos < CL.stride; pos += L.n * 16) {
+        uint32_t wd[4] = {0, 0, 0, 0};
+        if (pos == 0) {
+            wd[0] = (uint32_t)S | (uint32_t)t << 16;
+            wd[1] = (uint32_t)status;
+        } else if (pos < QFEC_CHECK_IDS) {
+            const uint64_t lo = pos == QFEC_CHECK_MARKS ? mk[0] : mk[2], hi = pos == QFEC_CHECK_MARKS ? mk[1] : mk[3];
+            wd[0] = (uint32_t)lo;
+            wd[1] = (uint32_t)(lo >> 32);
+            wd[2] = (uint32_t)hi;
+            wd[3] = (uint32_t)(hi >> 32);
+        } else if (pos < CL.a_off) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int i = pos - QFEC_CHECK_IDS + q;
+                if (i < nids)
+                    wd[q >> 2] |= (uint32_t)hdr[i < k ? PL.surv_off + i : PL.lost_off + e + (i - k)] << (8 * (q & 3));
+            }
+        } else if (pos < CL.r_off) {
+            const int i0 = pos - CL.a_off;
+            if (i0 < na) {
+                int x = i0 / k, c = i0 - x * k;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    if (i0 + q < na)
+                        wd[q >> 2] |= (uint32_t)(x ? plan_coef(C, PL, hdr, X, e, e + x, c) : row0[c]) << (8 * (q & 3));
+                    if (++c == k) { c = 0; ++x; }
+                }
+            }
+        } else {
+            const int i0 = pos - CL.r_off;
+            if (i0 < nr) {
+                int i = i0 / (S - 1), x = i0 - i * (S - 1);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    if (i0 + q < nr) {
+                        const uint8_t a0 = row0[i], ax = plan_coef(C, PL, hdr, X, e, e + 1 + x, i);
+                        const uint8_t r = a0 && ax ? C.gexp[C.glog[ax] + 255 - C.glog[a0]] : 0;
+                        wd[q >> 2] |= (uint32_t)r << (8 * (q & 3));
+                    }
+                    if (++x == S - 1) { x = 0; ++i; }
+                }
             }
         }
         L.store16(out + pos, wd);

@@ -16,6 +16,8 @@
 //   qfec_ptrs.cpp      qfec_encode_ptrs, qfec_reconstruct_ptrs (shards given as a device table of addresses)
 //   qfec_plan.cpp      qfec_plan_build / qfec_plan_apply, qfec_reconstruct_wide / qfec_repair_wide (decode plans
 //                      built on the device, any k + m), qfec_plan_build_host
+//   qfec_check.cpp     qfec_check_build / qfec_check_apply, qfec_locate_wide / qfec_scrub_wide (check plans built
+//                      on the device: single-shard error location at any k + m), qfec_check_build_host
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
@@ -240,6 +242,11 @@ struct qfec_code {
     // device plans (qfec_plan.cpp): is `full` empty or [I; rows]?  Judged once per version under mu
     uint64_t plan_chk_version = ~0ull;
     bool plan_chk_ok = false;
+    // check plans (qfec_check.cpp): are `rows` what qfec_code_new generates for (k, m), and why not?
+    // Judged once per version under mu
+    uint64_t check_chk_version = ~0ull;
+    int check_chk_rc = 0;
+    std::string check_chk_error;
 };
 
 namespace qfec {
@@ -270,6 +277,16 @@ int host_records(qfec_code* c, const uint8_t* marks, long long groups, std::vect
 int reconstruct_host_records(DevCtx& ctx, qfec_code* c, uint8_t* d_data, const uint8_t* d_par,
                              const uint8_t* d_marks, long long groups, int block_size, long long pitch,
                              unsigned* d_failed, hipStream_t s);
+
+// ---- device plans (qfec_plan.cpp)
+// QFEC_EUNSUP for a code whose rs.c decode matrix is not [I; rows] (an edited handle)
+int plan_code_check(const qfec_code* c, const char* who);
+// what the plan calls (qfec_plan.cpp, qfec_check.cpp) refuse before a device is touched: the cause of a
+// bad batch argument or nullptr; a plan base the 16-byte stores and dword loads cannot take; the
+// refusal itself, its cause named in the error text (returns QFEC_EINVAL)
+const char* bad_rows_args(const qfec_code* code, long long groups, int block_size, long long pitch);
+bool plan_misaligned(const void* d_plan);
+int refuse(const char* who, const char* why);
 
 // ---- shared by the locate family (qfec_locate.cpp)
 // Can single-shard location work on this code at all?  Decided on the host, before any device.
