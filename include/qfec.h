@@ -263,6 +263,50 @@ int qfec_repair_wide(qfec_code *code, unsigned char *d_data, unsigned char *d_pa
 int qfec_plan_build_host(const qfec_code *code, const unsigned char *marks_n, int mode,
                          unsigned char *out_plan /* stride bytes */);
 
+/* Device plans on shards SCATTERED in device memory: reconstruct AND repair on a pointer table, at
+ * any k + m.  The join of the two families above: the table, the marks and the shard rules are those
+ * of qfec_reconstruct_ptrs; the plans, the codes and the per-group results are those of
+ * qfec_plan_build / qfec_plan_apply / qfec_reconstruct_wide / qfec_repair_wide.
+ *   Table and marks: d_shards is a DEVICE array of groups * (k + m) device pointers in rs.c's shard
+ *     order (all data shards group-major, then all parity shards), d_marks the rs.c marks layout.
+ *   Shards: every shard is exactly block_size bytes at any alignment; no pitch, NO scratch bytes: no
+ *     byte outside [0, block_size) of any shard is read or written.
+ *   Codes: every code the plan calls accept, any k + m up to 256, narrow codes included.  QFEC_EUNSUP
+ *     only for an edited reed_solomon handle, as there.
+ *   Results: per group exactly those of qfec_plan_apply / qfec_reconstruct_wide / qfec_repair_wide on
+ *     the same rows laid out contiguously: the survivor rule (the k lowest unmarked ids), the same
+ *     coefficient bytes, the column-0 stale-row quirk (a flagged row starts from the destination's
+ *     previous bytes); status 0 groups and failed groups untouched, a singular group untouched and
+ *     counted.  qfec_plan_apply_ptrs counts nothing and never reads marks, so one plan (from
+ *     qfec_plan_build, 16-byte aligned, else QFEC_EINVAL) serves any number of tables.  The one-shot
+ *     calls count failed groups into *d_failed (device counter, may be NULL; accumulated, not reset).
+ *   Untouched shards: a shard the plan neither reads (it is not one of the k survivors) nor writes (it
+ *     is not in the lost list) is never dereferenced; its table entry still takes part in the
+ *     alignment judgement.
+ *   Alignment, judged per group on the device: a group all of whose k + m table entries are 16-B
+ *     aligned runs 16-byte lanes over its whole columns and the block_size % 16 tail bytes byte by
+ *     byte; any other group is worked on byte by byte, much slower.
+ *   Aliasing: shards that are only read may alias each other or repeat.  A shard the call writes must
+ *     not overlap any other shard of the batch, or the result is undefined.
+ *   Asynchronous on `stream`: no host synchronisation, no read-back.  The one-shot calls are
+ *     qfec_plan_build into stream-ordered scratch followed by qfec_plan_apply_ptrs, in chunks of at
+ *     most 64 MiB of plans; the scratch is freed on the stream.
+ *   Narrow codes (k + m <= 24): qfec_reconstruct_ptrs, which reads a prebuilt LUT and keeps the
+ *     survivors in registers, is the faster call there (DESIGN section 18 has the measured ratio);
+ *     qfec_reconstruct_ptrs_wide gives the same bytes and is the call for repair on pointers.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error after the call's name: a null code, groups < 0, block_size < 1, a null d_shards /
+ *     d_marks / d_plan with groups > 0, a d_plan that is not 16-byte aligned.  groups == 0 returns
+ *     QFEC_OK and launches nothing. */
+int qfec_plan_apply_ptrs(qfec_code *code, unsigned char *const *d_shards, const unsigned char *d_plan,
+                         long long groups, int block_size, void *stream);
+int qfec_reconstruct_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
+                               const unsigned char *d_marks, long long groups, int block_size,
+                               unsigned int *d_failed, void *stream);
+int qfec_repair_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
+                          const unsigned char *d_marks, long long groups, int block_size,
+                          unsigned int *d_failed, void *stream);
+
 /* Does the parity match the data?  Bit j of d_bad_rows[g] is set iff parity row j of group g
  * differs from rows[j] x data[g] (a true GF product) in any byte of [0, block_size); 0 = the group
  * is consistent.  d_bad_rows ([groups], may be NULL) is written for every group; *d_bad_groups
@@ -747,6 +791,11 @@ int qfec_probe_reconstruct(unsigned char *d_data, const unsigned char *d_parity,
  *                      through one copy in and one copy out.  Results and return codes are the same.
  *                      Host or mixed arrays, contiguous arrays and k + m > 24 (reconstruct) are not
  *                      affected
+ *   "rs_dev_ptrs_wide" 0 (default) | 1: with rs_dev_ptrs = 1, reed_solomon_reconstruct on such arrays with
+ *                      k + m > 24 builds RECONSTRUCT plans on the device and applies them on the caller's
+ *                      rows in place (qfec_reconstruct_ptrs_wide's kernels); 0 keeps the staged copies and
+ *                      host inversions.  Results and return codes are the same.  An edited handle,
+ *                      host or mixed arrays, k + m <= 24 and rs_dev_ptrs = 0 are not affected
  *   "percall_resident" 1 fec_encode / fec_decode of packets up to 4 KiB with k <= 16 and k * e <= 64
  *                      go to a resident one-block server that polls a request word in device memory
  *                      and exits by itself after percall_idle_us without a request | 0 one launch per

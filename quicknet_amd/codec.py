@@ -447,6 +447,33 @@ class Code:
         """repair for any k + m, asynchronous (qfec_repair_wide).  Arguments as for repair."""
         self._wide("qfec_repair_wide", data, parity, marks, block_size, failed, stream)
 
+    def plan_apply_ptrs(self, ptrs, plan, block_size, stream=None):
+        """Execute plans on shards scattered in device memory (qfec_plan_apply_ptrs).  ptrs as for
+        encode_ptrs; plan uint8 [G, plan_stride()] from plan_build, 16-byte aligned; each shard is
+        exactly block_size bytes, at any alignment.  Reads no marks and counts nothing."""
+        G = self._ptr_groups("plan_apply_ptrs", ptrs)
+        if plan.numel() != G * self.plan_stride():
+            raise QfecError(f"plan_apply_ptrs: plan has {plan.numel()} bytes for {G} groups of {self.plan_stride()}")
+        check(lib().qfec_plan_apply_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(plan, what="plan"), G,
+                                         int(block_size), _stream_handle(stream)), "qfec_plan_apply_ptrs")
+
+    def _ptrs_wide(self, name, ptrs, marks, block_size, failed, stream):
+        G = self._ptr_groups(name[5:], ptrs)
+        if marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"{name[5:]}: {marks.numel()} marks for {G} groups of ({self.k},{self.m})")
+        check(getattr(lib(), name)(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(marks, what="marks"), G,
+                                   int(block_size), _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), name)
+
+    def reconstruct_ptrs_wide(self, ptrs, marks, block_size, failed=None, stream=None):
+        """reconstruct_ptrs for any k + m, through device-built plans (qfec_reconstruct_ptrs_wide).
+        Arguments as for reconstruct_ptrs."""
+        self._ptrs_wide("qfec_reconstruct_ptrs_wide", ptrs, marks, block_size, failed, stream)
+
+    def repair_ptrs_wide(self, ptrs, marks, block_size, failed=None, stream=None):
+        """Rewrite every marked shard, data and parity, where it lies, for any k + m
+        (qfec_repair_ptrs_wide).  Arguments as for reconstruct_ptrs."""
+        self._ptrs_wide("qfec_repair_ptrs_wide", ptrs, marks, block_size, failed, stream)
+
     def plan_host(self, marks_n, mode):
         """The plan of one group-order mark vector over all n shards, computed on the CPU
         (qfec_plan_build_host): uint8 [plan_stride()] in the layout of include/qfec.h."""

@@ -312,6 +312,21 @@ struct PlanApplyArgs {
     int vec16;
 };
 
+// the same on a table of shard addresses (k_plan_apply_ptrs): the mapping and the geometry of the
+// pointer-table kernels (PtrsArgs), the plan of k_plan_apply
+struct PlanPtrsArgs {
+    const uint64_t* dptrs;    // [groups][k] addresses of the data shards of this launch's groups
+    const uint64_t* pptrs;    // [groups][m] addresses of their parity shards
+    const uint8_t* plan;      // [groups][stride] of this launch
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    uint64_t groups;
+    uint32_t block;           // bytes per shard
+    uint32_t stride;          // PlanLayout::stride
+    uint32_t vcols, wpg;      // whole 16-B columns per shard; waves per group (PtrsGeom at 16-B lanes)
+    uint32_t tail0, tailn;    // the bytes past the last whole column: first byte, count (< 16)
+    int k, m;
+};
+
 // device-built check plans (qfec_check.hip; layout and arithmetic in qfec_plan.hpp): single-shard
 // error location at any k + m.  k_check_build takes a PlanBuildArgs (dmarks NULL: nothing marked;
 // mode, quirk and failed unused; lds = QFEC_PLAN_GF_BYTES + check_work_bytes(k, m)).
@@ -435,6 +450,7 @@ struct Tuning {
     std::atomic<int> encode_block{-1};  // threads per encode block: -1 auto (64 for k = 10 all-rows), 64, 256
     std::atomic<int> encode_lds{-1};    // LDS bytes per encode block, capping waves per CU (-1 auto, 0 none)
     std::atomic<int> rs_dev_ptrs{0};    // module/rs.h on scattered device shards: 1 the pointer-table kernels in place, 0 staged copies
+    std::atomic<int> rs_dev_ptrs_wide{0};  // with rs_dev_ptrs 1: reconstruct of k + m > 24 through device plans on the table, 0 staged
 };
 Tuning& tuning();
 
@@ -455,6 +471,7 @@ hipError_t launch_locate_erased(const LocErasedArgs& a, hipStream_t stream);
 hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t stream);
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream);
+hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream);
 hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream);
 hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream);

@@ -9,9 +9,6 @@
 
 namespace qfec {
 
-// one chunk's plans in the one-shot calls stay under this many bytes of stream-ordered scratch
-constexpr long long kPlanScratchCap = 64ll << 20;
-
 // rs.c's decode with a partially inverted matrix is not reproduced here: a code that carries an
 // rs.c decode matrix must have it equal to [I; rows].  Judged once per code version.
 int plan_code_check(const qfec_code* cc, const char* who) {
@@ -56,9 +53,8 @@ static int enc_tables(qfec_code* code, DevCtx& ctx, uint32_t** tab) {
 }
 
 // plans of `gn` groups whose marks start at dmarks / pmarks
-static int run_plan_build(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint8_t* dmarks,
-                          const uint8_t* pmarks, long long gn, int mode, uint8_t* d_plan, unsigned* d_failed,
-                          hipStream_t s) {
+int run_plan_build(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint8_t* dmarks, const uint8_t* pmarks,
+                   long long gn, int mode, uint8_t* d_plan, unsigned* d_failed, hipStream_t s) {
     PlanBuildArgs a{};
     a.tab = tab;
     a.gf = ctx.d_gf;

@@ -12,8 +12,13 @@
 // indexes the 256-entry perm table.  With k in the hundreds the survivors cannot stay in registers:
 // the kernel loops over the k survivors and accumulates up to PCH output rows per pass, so for
 // t <= PCH every survivor byte is loaded once; above that each pass of PCH rows re-reads them.
+//
+// k_plan_apply_ptrs: the same column body (plan_column) where the rows are given by a device table of
+// shard addresses (qfec_plan_apply_ptrs), in the mapping of the pointer-table kernels of qfec_ptrs.hip.
 #include "qfec_device.hpp"
+#include "qfec_geom.hpp"
 #include "qfec_plan.hpp"
+#include "qfec_ptrs_device.hpp"
 
 namespace qfec {
 
@@ -46,27 +51,12 @@ __global__ void __launch_bounds__(64) k_plan_build(PlanBuildArgs a) {
 // byte idx of the plan through a scalar dword load
 __device__ __forceinline__ uint32_t plan_u8(cptr32 pw, int idx) { return (pw[idx >> 2] >> ((idx & 3) * 8)) & 0xFFu; }
 
-template <bool VEC16>
-__global__ void __launch_bounds__(256) k_plan_apply(PlanApplyArgs a, const uint8_t* __restrict__ plan) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t wid = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t g = wid / a.wpg;
-    const uint32_t part = wid - g * a.wpg;
-    if (g >= a.groups) return;
-    const int k = a.k, m = a.m, n = k + m;
-    const PlanLayout PL = plan_layout(k, m);
-    const cptr32 pw = (cptr32)(plan + (uint64_t)g * a.stride);
-    const cptr32 t256 = (cptr32)a.t256;
-    const int t = (int)(pw[0] & 0xFFFFu);
-    if ((pw[1] & 0xFFu) != (uint32_t)QFEC_PLAN_WORK || t > m) return;
-    const uint32_t col = part * 64u + lane;
-    if (col >= a.cols) return;
-    const uint64_t off = VEC16 ? (uint64_t)col * 16u : col;
-    uint8_t* data_g = a.data + (uint64_t)g * a.dgs;
-    uint8_t* par_g = a.parity + (uint64_t)g * a.pgs;
-    auto row = [&](uint32_t s) -> uint8_t* {
-        return s < (uint32_t)k ? data_g + (uint64_t)s * a.pitch : par_g + (uint64_t)(s - k) * a.pitch;
-    };
+// One column of a group through its plan: byte (VEC16: the 16 bytes at) `off` of the t listed rows
+// from the k survivors.  row(s) = where shard s of the group starts, s wave-uniform.  Where the ids
+// are not those of a plan of this code nothing more is done for the column.
+template <bool VEC16, class Row>
+__device__ __forceinline__ void plan_column(cptr32 pw, const PlanLayout& PL, cptr32 t256, int k, int n, int t,
+                                            const Row& row, uint64_t off) {
     using Acc = typename std::conditional<VEC16, uint4, uint32_t>::type;
 
     for (int j0 = 0; j0 < t; j0 += PCH) {
@@ -123,6 +113,80 @@ __global__ void __launch_bounds__(256) k_plan_apply(PlanApplyArgs a, const uint8
     }
 }
 
+template <bool VEC16>
+__global__ void __launch_bounds__(256) k_plan_apply(PlanApplyArgs a, const uint8_t* __restrict__ plan) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t wid = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t g = wid / a.wpg;
+    const uint32_t part = wid - g * a.wpg;
+    if (g >= a.groups) return;
+    const int k = a.k, m = a.m, n = k + m;
+    const PlanLayout PL = plan_layout(k, m);
+    const cptr32 pw = (cptr32)(plan + (uint64_t)g * a.stride);
+    const cptr32 t256 = (cptr32)a.t256;
+    const int t = (int)(pw[0] & 0xFFFFu);
+    if ((pw[1] & 0xFFu) != (uint32_t)QFEC_PLAN_WORK || t > m) return;
+    const uint32_t col = part * 64u + lane;
+    if (col >= a.cols) return;
+    const uint64_t off = VEC16 ? (uint64_t)col * 16u : col;
+    uint8_t* data_g = a.data + (uint64_t)g * a.dgs;
+    uint8_t* par_g = a.parity + (uint64_t)g * a.pgs;
+    auto row = [&](uint32_t s) -> uint8_t* {
+        return s < (uint32_t)k ? data_g + (uint64_t)s * a.pitch : par_g + (uint64_t)(s - k) * a.pitch;
+    };
+    plan_column<VEC16>(pw, PL, t256, k, n, t, row, off);
+}
+
+// The same on a table of shard addresses: the pointer-table kernels' mapping and geometry (a wave
+// per (group, slab of 64 16-B columns), the block % 16 tail and the byte body of a group with a
+// misaligned address: run_slab), plan_column for the work.  NP passes of 64 lanes hold the group's
+// k + m <= 64 * NP addresses, entry q * 64 + lane in register q of the lane, and the address of the
+// wave-uniform shard id s is a v_readlane of register s >> 6 at lane s & 63.
+// Every lane loads its entries before anything depends on the lane: a lane without a column of its
+// own (B = 16: all but one; the last wave of a row) still holds addresses the others read, so the
+// work below is predicated (run_slab) and no lane leaves early.  The alignment ballot uses the
+// loaded values, which also keeps the loads above the first lane-dependent branch.
+template <int NP>
+__global__ void __launch_bounds__(256) k_plan_apply_ptrs(PlanPtrsArgs a, const uint64_t* __restrict__ dptrs,
+                                                         const uint64_t* __restrict__ pptrs,
+                                                         const uint8_t* __restrict__ plan) {
+    const int lane = threadIdx.x & 63;
+    uint64_t g;
+    uint32_t slab;
+    if (!wave_item(a, &g, &slab)) return;
+    const int k = a.k, m = a.m, n = k + m;
+    uint64_t p[NP];
+    uint32_t low = 0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        p[q] = 0;
+        if (i < k) p[q] = dptrs[g * (uint64_t)k + i];
+        else if (i < n) p[q] = pptrs[g * (uint64_t)m + (i - k)];
+        low |= (uint32_t)p[q] & 15u;
+    }
+    const bool aligned = __ballot(low != 0) == 0;
+    const PlanLayout PL = plan_layout(k, m);
+    const cptr32 pw = (cptr32)(plan + g * a.stride);
+    const cptr32 t256 = (cptr32)a.t256;
+    const int t = (int)(pw[0] & 0xFFFFu);
+    if ((pw[1] & 0xFFu) != (uint32_t)QFEC_PLAN_WORK || t > m) return;  // wave-uniform
+    auto row = [&](uint32_t s) -> uint8_t* {
+        const uint32_t l = s & 63u;
+        if constexpr (NP == 1) return as_out(lane_value(p[0], l));
+        const uint32_t r = s >> 6;
+        if constexpr (NP == 2) return as_out(r == 0 ? lane_value(p[0], l) : lane_value(p[1], l));
+        else
+            return as_out(r == 0   ? lane_value(p[0], l)
+                          : r == 1 ? lane_value(p[1], l)
+                          : r == 2 ? lane_value(p[NP > 2 ? 2 : 0], l)
+                                   : lane_value(p[NP > 3 ? 3 : 0], l));
+    };
+    run_slab<16>(
+        a, slab, lane, aligned, [&](uint64_t off) { plan_column<true>(pw, PL, t256, k, n, t, row, off); },
+        [&](uint64_t b) { plan_column<false>(pw, PL, t256, k, n, t, row, b); });
+}
+
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream) {
     if (a.groups == 0) return hipSuccess;
     if (a.groups > 0x7FFFFFFFull / 64u || a.lds > 65536u) return hipErrorInvalidValue;  // caller chunks
@@ -137,6 +201,18 @@ hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream) {
     const unsigned grid = (unsigned)((waves + 3) / 4);
     if (a.vec16) hipLaunchKernelGGL((k_plan_apply<true>), dim3(grid), dim3(256), 0, stream, a, a.plan);
     else hipLaunchKernelGGL((k_plan_apply<false>), dim3(grid), dim3(256), 0, stream, a, a.plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    const uint64_t waves = a.groups * (uint64_t)a.wpg;
+    const int n = a.k + a.m;
+    if (a.wpg == 0 || waves * 64u > (uint64_t)kMaxLaunchLanes || n > 256) return hipErrorInvalidValue;  // caller chunks
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (n <= 64) hipLaunchKernelGGL((k_plan_apply_ptrs<1>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
+    else if (n <= 128) hipLaunchKernelGGL((k_plan_apply_ptrs<2>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
+    else hipLaunchKernelGGL((k_plan_apply_ptrs<4>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
     return hipGetLastError();
 }
 

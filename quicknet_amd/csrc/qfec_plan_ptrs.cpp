@@ -1,0 +1,109 @@
+// qfec_plan_ptrs.cpp -- device plans on pointer tables (include/qfec.h): qfec_plan_apply_ptrs and the
+// one-shot calls qfec_reconstruct_ptrs_wide / qfec_repair_ptrs_wide.  The plans are those of
+// qfec_plan.cpp (run_plan_build: they depend on the marks alone); the rows are where a device table
+// in module/rs.h's shard order says (qfec_ptrs.cpp), so a launch over groups [g0, g0 + gn) is handed
+// the two halves of the table, of the marks and the plans from g0 on.  Any k + m; arguments are
+// judged on the host before a device is touched; nothing is read back.
+#include "qfec_plan.hpp"
+#include "qfec_rt.hpp"
+
+namespace qfec {
+
+int run_plan_apply_ptrs(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
+                        const uint8_t* d_plan, long long gn, int block, hipStream_t s) {
+    PlanPtrsArgs a{};
+    const PtrsGeom p = ptrs_geom(block, 16);
+    a.t256 = ctx.d_t256;
+    a.k = c->k;
+    a.m = c->m;
+    a.block = (uint32_t)block;
+    a.stride = (uint32_t)plan_layout(c->k, c->m).stride;
+    a.vcols = p.vcols;
+    a.wpg = p.wpg;
+    a.tail0 = p.tail0;
+    a.tailn = p.tailn;
+    return for_group_chunks(gn, p.per, [&](long long g0, long long n) {
+        a.dptrs = dptrs + (size_t)g0 * a.k;
+        a.pptrs = pptrs + (size_t)g0 * a.m;
+        a.plan = d_plan + (size_t)g0 * a.stride;
+        a.groups = (uint64_t)n;
+        const hipError_t e = launch_plan_apply_ptrs(a, s);
+        return e == hipSuccess ? QFEC_OK : hip_fail(e, "plan_apply_ptrs kernel launch");
+    });
+}
+
+int run_wide_ptrs(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint64_t* dptrs, const uint64_t* pptrs,
+                  const uint8_t* dmarks, const uint8_t* pmarks, long long gn, int block, int mode, unsigned* d_failed,
+                  hipStream_t s, const char* who) {
+    const long long stride = plan_layout(c->k, c->m).stride;
+    const long long per = std::max(1ll, std::min(ptrs_geom(block, 16).per, kPlanScratchCap / stride));
+    return for_group_chunks(gn, per, [&](long long g0, long long n) {
+        uint8_t* plan = nullptr;
+        if (hipMallocAsync((void**)&plan, (size_t)n * stride, s) != hipSuccess)
+            return hip_fail(hipGetLastError(), (std::string(who) + " scratch").c_str());
+        int r = run_plan_build(ctx, c, tab, dmarks + (size_t)g0 * c->k, pmarks + (size_t)g0 * c->m, n, mode, plan,
+                               d_failed, s);
+        if (!r) r = run_plan_apply_ptrs(ctx, c, dptrs + (size_t)g0 * c->k, pptrs + (size_t)g0 * c->m, plan, n, block, s);
+        (void)hipFreeAsync(plan, s);
+        return r;
+    });
+}
+
+static const char* bad_ptrs_args(const qfec_code* code, long long groups, int block_size) {
+    return !code ? "null code" : groups < 0 ? "groups < 0" : block_size < 1 ? "block_size < 1" : nullptr;
+}
+
+static int one_shot(const char* who, qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_marks,
+                    long long groups, int block_size, int mode, unsigned* d_failed, hipStream_t s) {
+    const char* why = bad_ptrs_args(code, groups, block_size);
+    if (!why && groups > 0) why = !d_shards ? "null d_shards" : !d_marks ? "null d_marks" : nullptr;
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    int rc = batch_begin(who, false, [&] { return plan_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    uint32_t* tab = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(code->mu);
+        rc = ensure_enc(code, ctx->device, &tab);
+    }
+    if (rc) return rc;
+    const uint64_t* t = reinterpret_cast<const uint64_t*>(d_shards);
+    // rs.c layout, table and marks alike: every group's data entries, then the parity entries
+    return run_wide_ptrs(*ctx, code, tab, t, t + (size_t)groups * code->k, d_marks, d_marks + (size_t)groups * code->k,
+                         groups, block_size, mode, d_failed, s, who);
+}
+
+}  // namespace qfec
+
+using namespace qfec;
+
+extern "C" {
+
+int qfec_plan_apply_ptrs(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_plan, long long groups,
+                         int block_size, void* stream) {
+    const char* who = "qfec_plan_apply_ptrs";
+    const char* why = bad_ptrs_args(code, groups, block_size);
+    if (!why && groups > 0) why = !d_shards ? "null d_shards" : !d_plan ? "null d_plan" : nullptr;
+    if (!why && plan_misaligned(d_plan)) why = "d_plan not 16-byte aligned";
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    const int rc = batch_begin(who, false, [&] { return plan_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    const uint64_t* t = reinterpret_cast<const uint64_t*>(d_shards);
+    return run_plan_apply_ptrs(*ctx, code, t, t + (size_t)groups * code->k, d_plan, groups, block_size,
+                               (hipStream_t)stream);
+}
+
+int qfec_reconstruct_ptrs_wide(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_marks,
+                               long long groups, int block_size, unsigned int* d_failed, void* stream) {
+    return one_shot("qfec_reconstruct_ptrs_wide", code, d_shards, d_marks, groups, block_size, QFEC_PLAN_RECONSTRUCT,
+                    d_failed, (hipStream_t)stream);
+}
+
+int qfec_repair_ptrs_wide(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_marks,
+                          long long groups, int block_size, unsigned int* d_failed, void* stream) {
+    return one_shot("qfec_repair_ptrs_wide", code, d_shards, d_marks, groups, block_size, QFEC_PLAN_REPAIR, d_failed,
+                    (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -2,7 +2,8 @@
 // reconstruct / error (module/rs.h:22-49, module/rs.c:387-643).  Every caller shard pointer is
 // classified; arrays of host pointers run the two-slot pipelines below, contiguous device arrays run
 // in place, scattered device arrays are staged row by row or, with tuning "rs_dev_ptrs", handed to
-// the pointer-table kernels as they are; mixes are staged row by row.
+// the pointer-table kernels as they are (k + m > 24: "rs_dev_ptrs_wide", device plans on the table);
+// mixes are staged row by row.
 #include "qfec_rt.hpp"
 
 #include <immintrin.h>
@@ -169,12 +170,22 @@ void staged_report(const char* what, size_t ndev, size_t nptr) {
                 RsTrace::since(t_rs_entry) * 1e3, t_rs_classify * 1e3, ndev, nptr);
 }
 
+// plan_code_check as a question: the thread's error text is left as it was
+bool plan_code_ok(const qfec_code* c) {
+    const std::string keep = t_last_error;
+    const bool ok = plan_code_check(c, "reed_solomon_reconstruct") == QFEC_OK;
+    if (!ok) t_last_error = keep;
+    return ok;
+}
+
 // Tuning "rs_dev_ptrs" = 1, every shard in device memory but not back to back: the kernels of
 // qfec_ptrs.hip work on the caller's rows where they lie.  Per chunk of `per` groups the chunk's
 // addresses -- and, for the reconstruct (mk non-null), its marks -- go through the pinned stage in
 // the chunk's own rs.c layout with one H2D copy; every chunk has its own part of the stage, so
 // nothing waits before the one synchronisation at the end.  *nfail (reconstruct) is the device's
 // count of under-determined groups, read back after it.  Caller holds ctx.mu.
+// dec null with mk given (tuning "rs_dev_ptrs_wide", k + m > 24): no LUT; the chunk's RECONSTRUCT plans
+// are built on the device from its marks and applied on the table (run_wide_ptrs; tab: encode tables).
 int rs_ptrs_path(DevCtx& ctx, qfec_code* c, const uint32_t* tab, const DevLut* dec, unsigned char** data,
                  unsigned char** par, const uint8_t* mk, long long G, int B, long long per, long long* nfail) {
     const int k = c->k, m = c->m, n = k + m;
@@ -198,9 +209,11 @@ int rs_ptrs_path(DevCtx& ctx, qfec_code* c, const uint32_t* tab, const DevLut* d
         HIP_TRY(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, ctx.stream));
         const uint64_t* dp = reinterpret_cast<const uint64_t*>(ds);
         const uint64_t* pp = dp + (size_t)gn * k;
-        rc = mk ? run_reconstruct_ptrs(ctx, c, *dec, dp, pp, ds + pbytes, ds + pbytes + (size_t)gn * k, gn, B,
-                                       ctx.d_counter, ctx.stream)
-                : run_encode_ptrs(c, tab, dp, pp, gn, B, ctx.stream);
+        rc = !mk   ? run_encode_ptrs(c, tab, dp, pp, gn, B, ctx.stream)
+             : dec ? run_reconstruct_ptrs(ctx, c, *dec, dp, pp, ds + pbytes, ds + pbytes + (size_t)gn * k, gn, B,
+                                          ctx.d_counter, ctx.stream)
+                   : run_wide_ptrs(ctx, c, tab, dp, pp, ds + pbytes, ds + pbytes + (size_t)gn * k, gn, B,
+                                   QFEC_PLAN_RECONSTRUCT, ctx.d_counter, ctx.stream, "reed_solomon_reconstruct");
         if (rc) break;
         at += bytes;
     }
@@ -884,6 +897,26 @@ int reed_solomon_reconstruct(reed_solomon* rs, unsigned char** shards, unsigned 
             rc = rs_ptrs_path(*ctx, c, nullptr, &d->dec, data, par, mk, G, block_size, per, &nfail_all);
         }
         staged_report("reed_solomon_reconstruct (ptrs)", ndev_all, (size_t)G * n);
+        if (rc) {
+            fprintf(stderr, "[qfec] reed_solomon_reconstruct: %s\n", qfec_last_error());
+            return rc;
+        }
+        return nfail_all ? -1 : 0;
+    }
+    // the same arrays with k + m > 24, tuning "rs_dev_ptrs_wide" and an unedited handle: device plans on the table
+    if (tuning().rs_dev_ptrs && tuning().rs_dev_ptrs_wide && n > QFEC_LUT_MAX_N && ndev_all == (size_t)G * n &&
+        !(contiguous(data, (size_t)G * k, block_size) && contiguous(par, (size_t)G * m, block_size)) &&
+        plan_code_ok(c)) {
+        uint32_t* tab = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            rc = ensure_enc(c, ctx->device, &tab);
+        }
+        if (!rc) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            rc = rs_ptrs_path(*ctx, c, tab, nullptr, data, par, mk, G, block_size, per, &nfail_all);
+        }
+        staged_report("reed_solomon_reconstruct (ptrs wide)", ndev_all, (size_t)G * n);
         if (rc) {
             fprintf(stderr, "[qfec] reed_solomon_reconstruct: %s\n", qfec_last_error());
             return rc;

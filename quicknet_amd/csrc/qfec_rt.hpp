@@ -16,6 +16,8 @@
 //   qfec_ptrs.cpp      qfec_encode_ptrs, qfec_reconstruct_ptrs (shards given as a device table of addresses)
 //   qfec_plan.cpp      qfec_plan_build / qfec_plan_apply, qfec_reconstruct_wide / qfec_repair_wide (decode plans
 //                      built on the device, any k + m), qfec_plan_build_host
+//   qfec_plan_ptrs.cpp qfec_plan_apply_ptrs, qfec_reconstruct_ptrs_wide / qfec_repair_ptrs_wide (the plans applied to
+//                      shards given as a device table of addresses)
 //   qfec_check.cpp     qfec_check_build / qfec_check_apply, qfec_locate_wide / qfec_scrub_wide (check plans built
 //                      on the device: single-shard error location at any k + m), qfec_check_build_host
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
@@ -287,6 +289,20 @@ int plan_code_check(const qfec_code* c, const char* who);
 const char* bad_rows_args(const qfec_code* code, long long groups, int block_size, long long pitch);
 bool plan_misaligned(const void* d_plan);
 int refuse(const char* who, const char* why);
+// one chunk's plans in the one-shot calls stay under this many bytes of stream-ordered scratch
+constexpr long long kPlanScratchCap = 64ll << 20;
+// plans of `gn` groups whose marks start at dmarks / pmarks (tab: the code's encode tables on ctx's device)
+int run_plan_build(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint8_t* dmarks, const uint8_t* pmarks,
+                   long long gn, int mode, uint8_t* d_plan, unsigned* d_failed, hipStream_t s);
+// ---- device plans on pointer tables (qfec_plan_ptrs.cpp): dptrs / pptrs as for run_encode_ptrs
+// the plans of `gn` groups applied to the rows the table names; a launch over groups [g0, ..) of it
+// is handed dptrs + g0 * k, pptrs + g0 * m, plan + g0 * stride
+int run_plan_apply_ptrs(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
+                        const uint8_t* d_plan, long long gn, int block, hipStream_t s);
+// build into stream-ordered scratch, apply, free, in chunks of at most kPlanScratchCap of plans
+int run_wide_ptrs(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint64_t* dptrs, const uint64_t* pptrs,
+                  const uint8_t* dmarks, const uint8_t* pmarks, long long gn, int block, int mode, unsigned* d_failed,
+                  hipStream_t s, const char* who);
 
 // ---- shared by the locate family (qfec_locate.cpp)
 // Can single-shard location work on this code at all?  Decided on the host, before any device.

@@ -668,6 +668,7 @@ const std::vector<Knob>& knob_table() {
         {"encode_lds", &tuning().encode_lds, -1, 163840},
         {"encode_block", &tuning().encode_block, -1, 256},
         {"rs_dev_ptrs", &tuning().rs_dev_ptrs, 0, 1},
+        {"rs_dev_ptrs_wide", &tuning().rs_dev_ptrs_wide, 0, 1},
     };
     return t;
 }
