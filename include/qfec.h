@@ -155,6 +155,58 @@ int qfec_reconstruct_ptrs(qfec_code *code, unsigned char *const *d_shards,
                           const unsigned char *d_marks, long long groups, int block_size,
                           unsigned int *d_failed, void *stream);
 
+/* The pointer-table calls on shards that each have their OWN LENGTH: the packets of a FEC group as
+ * they lie, with no copy into zero-padded slots.  A data shard shorter than its group counts as
+ * zero-filled up to the group's length, and parity covers the group's longest shard only -- the
+ * reference's groupMaxPktSize (network/FecCodecBuf.cpp:137-156, fec_decode_pkts(.., maxSize)
+ * :197-206).  d_shards and d_marks are exactly those of qfec_encode_ptrs / qfec_reconstruct_ptrs:
+ * shard order, marks layout, any alignment and the aliasing rule carry over.  d_lens: DEVICE array of
+ * groups * k ints, the length of every data shard in table order.  max_len >= 1 is the longest
+ * length any group may have; it only sizes the launch.  Asynchronous on `stream`, no read-back; the
+ * tables must stay valid until the work has run.  Codes as for the fixed-length calls: any code for
+ * the encode; k + m <= 24 for the reconstruct through the same device LUT (QFEC_EUNSUP above that,
+ * qfec_prepare_reconstruct applies).
+ *   Encode, per group g, len_i = d_lens[g*k + i] and L = max_i len_i:
+ *     Void group: any len_i < 0 or > max_len (INT_MIN and INT_MAX included).  No byte of it is read
+ *       or written, d_group_len[g] = -1 and *d_invalid gains 1.
+ *     Empty group, L = 0: nothing is read or written, d_group_len[g] = 0.
+ *     Otherwise d_group_len[g] = L, and bytes [0, L) of every parity shard become exactly what
+ *       qfec_encode_ptrs with block_size = L writes for these shards zero-padded to L: the same
+ *       tables, the rs.c column-0 stale-row quirk included (a flagged row starts from the
+ *       destination's previous bytes).  Bytes [L, ...) of a parity shard are never written.
+ *     Data shard i is read in [0, len_i) only: no byte at or past len_i is read on any path, and
+ *       none influences a result.  A shard with len_i = 0 is never dereferenced (its table entry
+ *       may be anything) and takes no part in the alignment judgement.
+ *     d_group_len (groups ints, written) and d_invalid (one counter, accumulated, not reset) may
+ *       be NULL.  A sender transmits d_group_len[g] bytes of each parity shard of group g.
+ *   Reconstruct, per group g, L = d_group_len[g]: the length of the group's parity shards -- what
+ *     the encode reported, what a receiver reads off a parity packet.
+ *     Lengths are judged before marks.  The group is untouched and counted into *d_invalid (not
+ *       into *d_failed) when L is outside [0, max_len] or an unmarked data shard has len_i outside
+ *       [0, L].  Then an empty group, L = 0, is untouched and counted nowhere.
+ *     The d_lens entry of a marked data shard is not looked at.  The shard has room for L bytes
+ *       and exactly its bytes [0, L) are written.
+ *     Otherwise the behaviour is that of qfec_reconstruct_ptrs with block_size = L on the
+ *       zero-padded rows: the same survivor rule (all surviving data, then the first e surviving
+ *       parity rows), records, quirk and *d_failed accounting; groups with no erased data are
+ *       untouched; under-determined groups are untouched and counted into *d_failed.
+ *     Surviving data shard i is read in [0, len_i), the parity survivors used in [0, L); nothing
+ *       else is dereferenced.
+ *   Alignment, per group: a group runs 16-byte (reconstruct of k >= 10: 8-byte) accesses over its
+ *     whole columns when all of its table entries that the call may dereference are 16-B aligned;
+ *     any other group is worked on byte by byte, much slower.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error: a null code, groups < 0, max_len < 1, and with groups > 0 a null d_shards, a
+ *     null d_lens, a null d_marks or (reconstruct only) a null d_group_len.  groups == 0 (or m == 0
+ *     for the encode) returns QFEC_OK and launches nothing. */
+int qfec_encode_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                         const int *d_lens, long long groups, int max_len,
+                         int *d_group_len, unsigned int *d_invalid, void *stream);
+int qfec_reconstruct_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                              const int *d_lens, const int *d_group_len,
+                              const unsigned char *d_marks, long long groups, int max_len,
+                              unsigned int *d_failed, unsigned int *d_invalid, void *stream);
+
 /* Host-side decode-matrix query for one group (group-order marks[n]).  Writes e <= m
  * rows of k coefficients over the survivors listed in survivors[k] (shard ids 0..n-1).
  * Returns e, 0 when nothing is erased, or -1 when under-determined.  CPU only. */

@@ -19,6 +19,7 @@ EXPORTS = {
                "qfec_encode", "qfec_encode_host", "qfec_reconstruct", "qfec_reconstruct_host", "qfec_prepare_reconstruct", "qfec_decode_rows",
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
                "qfec_encode_update", "qfec_update", "qfec_encode_ptrs", "qfec_reconstruct_ptrs",
+               "qfec_encode_ptrs_var", "qfec_reconstruct_ptrs_var",
                "qfec_plan_stride", "qfec_plan_build", "qfec_plan_apply", "qfec_reconstruct_wide", "qfec_repair_wide",
                "qfec_plan_build_host", "qfec_plan_apply_ptrs", "qfec_reconstruct_ptrs_wide", "qfec_repair_ptrs_wide",
                "qfec_check_stride", "qfec_check_build", "qfec_check_apply", "qfec_locate_wide", "qfec_scrub_wide",
@@ -92,6 +93,8 @@ def lib():
         "qfec_update": (i, [vp, vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_encode_ptrs": (i, [vp, vp, ll, i, vp]),
         "qfec_reconstruct_ptrs": (i, [vp, vp, vp, ll, i, vp, vp]),
+        "qfec_encode_ptrs_var": (i, [vp, vp, vp, ll, i, vp, vp, vp]),
+        "qfec_reconstruct_ptrs_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp]),
         "qfec_plan_stride": (ll, [vp]),
         "qfec_plan_build": (i, [vp, vp, ll, i, vp, vp, vp]),
         "qfec_plan_apply": (i, [vp, vp, vp, vp, ll, i, ll, vp]),

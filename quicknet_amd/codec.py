@@ -296,6 +296,46 @@ class Code:
                                           int(block_size), _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)),
               "qfec_reconstruct_ptrs")
 
+    @staticmethod
+    def _int32_count(what, name, t, count):
+        import torch
+        if t.dtype != torch.int32:
+            raise QfecError(f"{what}: {name} has dtype {t.dtype}, int32 expected")
+        if t.numel() != count:
+            raise QfecError(f"{what}: {name} has {t.numel()} elements, {count} expected")
+
+    def encode_ptrs_var(self, ptrs, lens, max_len, group_len=None, invalid=None, stream=None):
+        """qfec_encode_ptrs_var: encode_ptrs on shards that each have their own length.  ptrs as for
+        encode_ptrs; lens: int32 [G*k] on device, the length of every data shard in table order; max_len:
+        the longest length any group may have.  group_len: optional int32 [G] on device, written (-1 for
+        a void group, else the group's longest length: the bytes of each parity shard that count);
+        invalid: optional device int32/uint32 [1] counter of void groups (accumulates)."""
+        G = self._ptr_groups("encode_ptrs_var", ptrs)
+        self._int32_count("encode_ptrs_var", "lens", lens, G * self.k)
+        if group_len is not None:
+            self._int32_count("encode_ptrs_var", "group_len", group_len, G)
+        check(lib().qfec_encode_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"), G,
+                                         int(max_len), _dev_ptr(group_len, _I32, "group_len"),
+                                         _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_encode_ptrs_var")
+
+    def reconstruct_ptrs_var(self, ptrs, lens, group_len, marks, max_len, failed=None, invalid=None, stream=None):
+        """qfec_reconstruct_ptrs_var: reconstruct_ptrs on shards that each have their own length.  ptrs,
+        marks and failed as for reconstruct_ptrs; lens: int32 [G*k] on device (the entries of marked
+        shards are not looked at); group_len: int32 [G] on device, the length of every group's parity
+        shards, as encode_ptrs_var reported it; invalid: optional device int32/uint32 [1] counter of
+        groups refused for their lengths (accumulates)."""
+        G = self._ptr_groups("reconstruct_ptrs_var", ptrs)
+        if marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"reconstruct_ptrs_var: {marks.numel()} marks for {G} groups of ({self.k},{self.m})")
+        self._int32_count("reconstruct_ptrs_var", "lens", lens, G * self.k)
+        self._int32_count("reconstruct_ptrs_var", "group_len", group_len, G)
+        check(lib().qfec_reconstruct_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                              _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(marks, what="marks"), G,
+                                              int(max_len), _dev_ptr(failed, _I32, "failed"),
+                                              _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_reconstruct_ptrs_var")
+
     def prepare_repair(self):
         check(lib().qfec_prepare_repair(self._h), "qfec_prepare_repair")
 

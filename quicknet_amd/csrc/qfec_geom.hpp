@@ -100,6 +100,32 @@ inline PtrsGeom ptrs_geom(int block, int lane_bytes) {
     return p;
 }
 
+// The pointer-table calls with per-shard lengths (qfec_encode_ptrs_var, qfec_reconstruct_ptrs_var):
+// the launch has ptrs_geom(max_len, lane_bytes).wpg waves per group, and every group cuts its own
+// length L <= max_len inside the kernel by this rule, which the host can call as well
+// (tests/test_ptrs_var_host.py).  Waves [0, live) of the group have work; a wave whose slab starts
+// at or past L (slab >= live) leaves.  The whole columns go to the vector body, the L % lane_bytes
+// bytes after them byte by byte to the first lanes of wave live - 1.  L = 0: no live wave.
+#ifdef __HIPCC__
+#define QFEC_GEOM_HD __host__ __device__
+#else
+#define QFEC_GEOM_HD
+#endif
+struct PtrsVarGeom {
+    uint32_t live;          // waves of the group with work: ceil(L / (64 * lane_bytes))
+    uint32_t vcols;         // whole columns
+    uint32_t tail0, tailn;  // first byte and count of the tail (tailn < lane_bytes; tail0 + tailn = L)
+};
+
+QFEC_GEOM_HD inline PtrsVarGeom ptrs_var_geom(uint32_t len, uint32_t lane_bytes) {
+    PtrsVarGeom v;
+    v.vcols = len / lane_bytes;
+    v.tail0 = v.vcols * lane_bytes;
+    v.tailn = len - v.tail0;
+    v.live = (v.vcols + (v.tailn ? 1u : 0u) + 63u) / 64u;
+    return v;
+}
+
 // The datagram / frame send (qfec_pack_datagrams, qfec_pack_frames; kernels in qfec_wire.hip): which
 // kernels a call takes.  `row_pitch` is the wire pitch, or the frame pitch with a frame prefix (4, or
 // 12 with the Session words); `instance`: a compile-time (k, m) exists and the fused send is on.

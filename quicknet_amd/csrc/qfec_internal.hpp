@@ -171,6 +171,17 @@ struct PtrsArgs {
     int surv_off, lost_off, hdr, coff;  // RecordLayout
 };
 
+// the same with per-shard lengths (qfec_ptrs_var.hip): p is what the fixed-length kernels take, with
+// block = max_len and the geometry of max_len, which only sizes the launch (wpg, lane_bytes); every
+// group cuts its own length inside the kernel (ptrs_var_geom)
+struct PtrsVarArgs {
+    PtrsArgs p;
+    const int32_t* lens;         // [groups][k] lengths of the data shards of this launch's groups
+    int32_t* group_len_out;      // encode: [groups] written (-1 void, else the longest length); may be NULL
+    const int32_t* group_len;    // reconstruct: [groups] length of the group's parity shards
+    unsigned int* invalid;       // counter of groups refused for their lengths; may be NULL
+};
+
 // single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
 // syndrome tests every data shard as the culprit
 struct LocateArgs {
@@ -462,6 +473,8 @@ hipError_t launch_encode_update(const EncUpdateArgs& a, hipStream_t stream);
 hipError_t launch_update(const UpdateArgs& a, hipStream_t stream);
 hipError_t launch_encode_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs(const PtrsArgs& a, hipStream_t stream);
+hipError_t launch_encode_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
+hipError_t launch_reconstruct_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);

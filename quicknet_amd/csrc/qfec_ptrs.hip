@@ -78,41 +78,7 @@ __device__ __forceinline__ void encode_byte(int k, int m, const uint32_t* tab, c
     }
 }
 
-// the M parity columns at byte `off` from the K data columns there.  For K >= 16 the inputs come in
-// two halves, as in k_encode_perm_halves: half the input registers live at a time.
-template <int K, int M>
-__device__ __forceinline__ void encode_column(const uint8_t* const (&src)[K], uint8_t* const (&dst)[M],
-                                              const uint32_t* tab, uint64_t off) {
-    uint4 acc[M];
-#pragma unroll
-    for (int r = 0; r < M; ++r) {
-        acc[r] = make_uint4(0, 0, 0, 0);
-        if (tab[(r * K) * QFEC_TAB_STRIDE + 5]) acc[r] = *reinterpret_cast<const uint4*>(dst[r] + off);  // rs.c column-0 quirk
-    }
-    if constexpr (K >= 16) {
-        constexpr int H = (K + 1) / 2;
-        {
-            uint4 x[H];
-#pragma unroll
-            for (int c = 0; c < H; ++c) x[c] = ld16(src[c] + off);
-            enc_mac16<K, M, 0, H>(acc, x, tab);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
-        {
-            uint4 x[K - H];
-#pragma unroll
-            for (int c = 0; c < K - H; ++c) x[c] = ld16(src[H + c] + off);
-            enc_mac16<K, M, H, K - H>(acc, x, tab);
-        }
-    } else {
-        uint4 x[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) x[c] = ld16(src[c] + off);
-        enc_mac16<K, M, 0, K>(acc, x, tab);
-    }
-#pragma unroll
-    for (int r = 0; r < M; ++r) st16(dst[r] + off, acc[r]);
-}
+// the vector body, encode_column, is in qfec_ptrs_device.hpp (qfec_ptrs_var.hip runs it too)
 
 // __restrict__ parameters: the address table and the encode tables are not written by the launch,
 // so their loads need not be ordered against the stores

@@ -1,12 +1,15 @@
 // qfec_ptrs_device.hpp -- what the kernels on tables of shard addresses share (qfec_ptrs.hip: encode,
-// reconstruct; qfec_plan.hip: k_plan_apply_ptrs): reading an address out of the lane that loaded it,
-// saying that it is global memory, and a wave's share of its group's shards.
+// reconstruct; qfec_ptrs_var.hip: the same with per-shard lengths; qfec_plan.hip: k_plan_apply_ptrs):
+// reading an address out of the lane that loaded it, saying that it is global memory, a wave's share
+// of its group's shards, and the encode's vector body on row addresses.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "qfec_device.hpp"
 
 namespace qfec {
 
@@ -54,6 +57,42 @@ __device__ __forceinline__ bool wave_item(const Args& a, uint64_t* g, uint32_t* 
     *g = wid / a.wpg;
     *slab = wid - (uint32_t)*g * a.wpg;
     return *g < a.groups;
+}
+
+// the M parity columns at byte `off` from the K data columns there.  For K >= 16 the inputs come in
+// two halves, as in k_encode_perm_halves: half the input registers live at a time.
+template <int K, int M>
+__device__ __forceinline__ void encode_column(const uint8_t* const (&src)[K], uint8_t* const (&dst)[M],
+                                              const uint32_t* tab, uint64_t off) {
+    uint4 acc[M];
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+        acc[r] = make_uint4(0, 0, 0, 0);
+        if (tab[(r * K) * QFEC_TAB_STRIDE + 5]) acc[r] = *reinterpret_cast<const uint4*>(dst[r] + off);  // rs.c column-0 quirk
+    }
+    if constexpr (K >= 16) {
+        constexpr int H = (K + 1) / 2;
+        {
+            uint4 x[H];
+#pragma unroll
+            for (int c = 0; c < H; ++c) x[c] = ld16(src[c] + off);
+            enc_mac16<K, M, 0, H>(acc, x, tab);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
+        {
+            uint4 x[K - H];
+#pragma unroll
+            for (int c = 0; c < K - H; ++c) x[c] = ld16(src[H + c] + off);
+            enc_mac16<K, M, H, K - H>(acc, x, tab);
+        }
+    } else {
+        uint4 x[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) x[c] = ld16(src[c] + off);
+        enc_mac16<K, M, 0, K>(acc, x, tab);
+    }
+#pragma unroll
+    for (int r = 0; r < M; ++r) st16(dst[r] + off, acc[r]);
 }
 
 }  // namespace qfec
