@@ -470,6 +470,58 @@ int qfec_scrub(qfec_code *code, unsigned char *d_data, unsigned char *d_parity,
  * qfec_repair_rows. */
 int qfec_locate_ratios(const qfec_code *code, unsigned char *out /* k*(m-1): r_{j,i} at [i*(m-1)+(j-1)] */);
 
+/* The integrity family on pointer tables: qfec_verify, qfec_locate and a scrub on shards scattered
+ * in device memory, without a copy into a contiguous batch.
+ *   Table and shards: exactly qfec_encode_ptrs' -- groups * (k + m) device addresses, every group's
+ *     k data shards first (group-major), then every group's m parity shards; every shard is exactly
+ *     block_size bytes, at any alignment, and no byte outside [0, block_size) of a shard is read.
+ *     qfec_verify_ptrs and qfec_locate_ptrs write nothing into any shard, so there shards may alias
+ *     each other or repeat.  In qfec_scrub_ptrs a shard that gets rewritten must not overlap any other
+ *     shard of the batch (qfec_repair_ptrs_wide's rule), or the result is undefined.
+ *   Results: per group exactly those of the contiguous calls on the same rows laid out contiguously.
+ *     qfec_verify_ptrs: d_bad_rows ([groups], may be NULL) holds qfec_verify's bits (a true GF
+ *       product, no stale-row quirk) and is written for every group; *d_bad_groups (device counter,
+ *       may be NULL; accumulated, not reset) gains 1 per inconsistent group, exactly once.  With both
+ *       NULL the call returns QFEC_OK and launches nothing; with m == 0 every word is 0.
+ *     qfec_locate_ptrs: d_culprit, d_marks and d_counts are what qfec_locate gives -- an id in
+ *       0 .. k+m-1 or QFEC_LOC_CLEAN / QFEC_LOC_MULTI / QFEC_LOC_AMBIGUOUS, with its m = 2 caveat.
+ *       d_marks (groups * (k + m) bytes, may be NULL) comes back in the table's own order and can be
+ *       handed unchanged to qfec_repair_ptrs_wide.
+ *     qfec_scrub_ptrs: qfec_locate_ptrs into stream-ordered scratch marks (the culprits too when
+ *       d_culprit is NULL), then the repair qfec_repair_ptrs_wide runs with those marks.  A group with
+ *       one corrupted shard is back to its original bytes; CLEAN, MULTI and AMBIGUOUS groups are
+ *       untouched byte for byte; a located group whose plan is singular (explicit non-MDS rows only)
+ *       is untouched and counted into *d_failed (device counter, may be NULL; accumulated).
+ *   Codes: qfec_verify_ptrs takes any k with m <= 32, as qfec_verify (k + m may pass 64).
+ *     qfec_locate_ptrs has qfec_locate's limits: m >= 2, k <= 32, m <= 32, no zero coefficient.
+ *     qfec_scrub_ptrs takes the codes both its halves accept: qfec_locate's limits, and not a
+ *     reed_solomon handle whose matrix was edited (the plan calls' refusal).  It has NO k + m <= 24
+ *     limit, which is more than qfec_scrub offers: the repair goes through device-built plans, not
+ *     the repair LUT.  QFEC_EUNSUP is decided on the host before a device is touched.
+ *   Alignment, judged per group on the device: a group all of whose k + m table entries are 16-B
+ *     aligned runs 16-byte lanes over its whole columns and the block_size % 16 tail bytes byte by
+ *     byte; any other group is worked on byte by byte, much slower.
+ *   Asynchronous on `stream`: no host synchronisation, no read-back; the per-group working words
+ *     come from stream-ordered scratch.  A batch beyond one launch's index space goes in several.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error after the call's name: a null code, groups < 0, block_size < 1, a null d_shards
+ *     with groups > 0, and for qfec_locate_ptrs a null d_culprit with groups > 0.  groups == 0 returns
+ *     QFEC_OK and launches nothing. */
+int qfec_verify_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                     long long groups, int block_size,
+                     unsigned int *d_bad_rows   /* [groups], nullable */,
+                     unsigned int *d_bad_groups /* counter, accumulates, nullable */, void *stream);
+int qfec_locate_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                     long long groups, int block_size,
+                     int *d_culprit             /* [groups]: shard id 0..k+m-1, or QFEC_LOC_* */,
+                     unsigned char *d_marks     /* rs.c layout, groups*(k+m) bytes, nullable */,
+                     unsigned int *d_counts     /* [3] located, multi, ambiguous; accumulates; nullable */,
+                     void *stream);
+int qfec_scrub_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                    long long groups, int block_size,
+                    int *d_culprit /* nullable */, unsigned int *d_counts /* [3], nullable */,
+                    unsigned int *d_failed /* nullable, accumulates */, void *stream);
+
 /* Which TWO shards are wrong?  qfec_locate stops at one corrupted shard per group and calls the rest
  * MULTI.  A code with m >= 4 parity rows has minimum distance m + 1 >= 5 and determines two corrupted
  * shards uniquely.  With H = [rows | I_m], h_x = column x of the parity rows for a data shard x < k

@@ -25,6 +25,7 @@ EXPORTS = {
                "qfec_check_stride", "qfec_check_build", "qfec_check_apply", "qfec_locate_wide", "qfec_scrub_wide",
                "qfec_check_build_host",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
+               "qfec_verify_ptrs", "qfec_locate_ptrs", "qfec_scrub_ptrs",
                "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
                "qfec_pipe_new", "qfec_pipe_free", "qfec_pipe_encode", "qfec_pipe_reconstruct", "qfec_pipe_wait", "qfec_pipe_slots",
@@ -113,6 +114,9 @@ def lib():
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),
+        "qfec_verify_ptrs": (i, [vp, vp, ll, i, vp, vp, vp]),
+        "qfec_locate_ptrs": (i, [vp, vp, ll, i, vp, vp, vp, vp]),
+        "qfec_scrub_ptrs": (i, [vp, vp, ll, i, vp, vp, vp, vp]),
         "qfec_locate2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate2_checks": (i, [vp, i, i, vp]),

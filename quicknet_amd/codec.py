@@ -514,6 +514,58 @@ class Code:
         (qfec_repair_ptrs_wide).  Arguments as for reconstruct_ptrs."""
         self._ptrs_wide("qfec_repair_ptrs_wide", ptrs, marks, block_size, failed, stream)
 
+    def _ptrs_out(self, what, ptrs, out, out_name, counts=None):
+        """The checks verify_ptrs / locate_ptrs / scrub_ptrs share -> (G, out): out is the call's
+        per-group device int32 [G] result, allocated when not given; counts is checked when given."""
+        import torch
+        G = self._ptr_groups(what, ptrs)
+        if out is None:
+            out = torch.empty(G, dtype=torch.int32, device=ptrs.device)
+        else:
+            if out.numel() != G:
+                raise QfecError(f"{what}: {out_name} has {out.numel()} elements for {G} groups")
+            if out.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise QfecError(f"{what}: {out_name} has dtype {out.dtype}, a 4-byte integer expected")
+        if counts is not None and counts.numel() != 3:
+            raise QfecError(f"{what}: counts has {counts.numel()} elements, not 3")
+        return G, out
+
+    def verify_ptrs(self, ptrs, block_size, bad_rows=None, bad_groups=None, stream=None):
+        """verify() on shards scattered in device memory (qfec_verify_ptrs).  ptrs as for encode_ptrs;
+        nothing is written into a shard.  Returns bad_rows, a device int32 [G] tensor (allocated when
+        not given) with verify()'s bits; bad_groups: optional device int32/uint32 [1] counter that
+        gains 1 per inconsistent group (accumulates)."""
+        G, bad_rows = self._ptrs_out("verify_ptrs", ptrs, bad_rows, "bad_rows")
+        check(lib().qfec_verify_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
+                                     _dev_ptr(bad_rows, _I32, "bad_rows"), _dev_ptr(bad_groups, _I32, "bad_groups"),
+                                     _stream_handle(stream)), "qfec_verify_ptrs")
+        return bad_rows
+
+    def locate_ptrs(self, ptrs, block_size, culprit=None, marks=None, counts=None, stream=None):
+        """locate() on shards scattered in device memory (qfec_locate_ptrs).  ptrs as for encode_ptrs;
+        nothing is written into a shard.  Returns culprit as locate() does.  marks: optional device
+        uint8 [G*k + G*m] in the table's own order, written for every group -- ready for
+        repair_ptrs_wide(); counts: optional device int32/uint32 [3] located / multi / ambiguous."""
+        G, culprit = self._ptrs_out("locate_ptrs", ptrs, culprit, "culprit", counts)
+        if marks is not None and marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"locate_ptrs: marks has {marks.numel()} elements for {G} groups of {self.k + self.m}")
+        check(lib().qfec_locate_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
+                                     _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks, what="marks"),
+                                     _dev_ptr(counts, _I32, "counts"), _stream_handle(stream)), "qfec_locate_ptrs")
+        return culprit
+
+    def scrub_ptrs(self, ptrs, block_size, culprit=None, counts=None, failed=None, stream=None):
+        """locate_ptrs() + repair_ptrs_wide() of the located shard in one call (qfec_scrub_ptrs), at any
+        k + m locate() takes: a group with one corrupted shard is rewritten to its original bytes where
+        it lies, MULTI / AMBIGUOUS groups are left as they are and only reported.  failed: optional
+        device int32/uint32 [1] counter of located groups with a singular plan (accumulates).  Returns
+        culprit as locate() does."""
+        G, culprit = self._ptrs_out("scrub_ptrs", ptrs, culprit, "culprit", counts)
+        check(lib().qfec_scrub_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
+                                    _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                                    _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_scrub_ptrs")
+        return culprit
+
     def plan_host(self, marks_n, mode):
         """The plan of one group-order mark vector over all n shards, computed on the CPU
         (qfec_plan_build_host): uint8 [plan_stride()] in the layout of include/qfec.h."""

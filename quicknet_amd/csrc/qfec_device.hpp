@@ -1,7 +1,8 @@
 // qfec_device.hpp -- device helpers shared by the HIP kernels of libqfec (gfx950).
 // GF(2^8) multiply by a constant four bytes per v_perm_b32 (see qfec_kernels.hip header),
 // streamed loads/stores, division by a runtime constant, the bodies the integrity kernels share
-// (qfec_verify.hip, qfec_locate.hip, qfec_locate_erased.hip): products, reports, counters, marks,
+// (qfec_verify.hip, qfec_locate.hip, qfec_locate_erased.hip, qfec_integrity_ptrs.hip): products,
+// syndrome tests, reports, counters, marks,
 // and the encode's and the reconstruct's column bodies, which the contiguous kernels
 // (qfec_kernels.hip) and the pointer-table kernels (qfec_ptrs.hip) both run.
 #pragma once
@@ -302,6 +303,22 @@ __device__ __forceinline__ uint4 column_mask(uint32_t block, uint32_t col) {
 
 __device__ __forceinline__ bool differs(const uint4& acc, const uint4& p, const uint4& mk) {
     return (((acc.x ^ p.x) & mk.x) | ((acc.y ^ p.y) & mk.y) | ((acc.z ^ p.z) & mk.z) | ((acc.w ^ p.w) & mk.w)) != 0;
+}
+
+// ------------------------------------------------------------------ syndromes of 16 bytes
+// (qfec_locate.hip, qfec_integrity_ptrs.hip)
+
+__device__ __forceinline__ bool same16(const uint4& a, const uint4& b) {
+    return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) == 0;
+}
+
+__device__ __forceinline__ bool nonzero16(const uint4& s) { return (s.x | s.y | s.z | s.w) != 0; }
+
+// r x s0 over 16 bytes == sj ?  (both are zero in the masked bytes)
+__device__ __forceinline__ bool ratio_holds(const Sel (&s0)[4], const uint4& sj, const uint32_t* __restrict__ r) {
+    uint4 pr = make_uint4(0, 0, 0, 0);
+    gf_mac16(pr, s0, r);
+    return same16(pr, sj);
 }
 
 // ------------------------------------------------------------------ P x data on the flat mapping

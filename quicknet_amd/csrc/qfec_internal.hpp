@@ -182,6 +182,23 @@ struct PtrsVarArgs {
     unsigned int* invalid;       // counter of groups refused for their lengths; may be NULL
 };
 
+// parity check and single-shard error location on a table of shard addresses
+// (qfec_integrity_ptrs.hip): PtrsArgs' mapping on 16-B lanes, the group words of VerifyArgs / LocateArgs
+struct IntegrityPtrsArgs {
+    const uint64_t* dptrs;    // [groups][k] addresses of the data shards of this launch's groups
+    const uint64_t* pptrs;    // [groups][m] addresses of their parity shards
+    const uint32_t* tab;      // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    const uint32_t* rtab;     // locate: [k][m-1][QFEC_TAB_STRIDE], as LocateArgs
+    unsigned int* bad_rows;   // [groups] of this launch, zeroed before it
+    unsigned int* cand;       // locate: [groups] of this launch, all ones before it
+    unsigned int* bad_groups; // verify: counter of groups with any bad row; may be NULL
+    uint64_t groups;
+    uint32_t block;           // bytes per shard
+    uint32_t vcols, wpg;      // whole 16-B columns per shard; waves per group (PtrsGeom)
+    uint32_t tail0, tailn;    // the bytes past the last whole column: first byte, count (< 16)
+    int k, m;                 // verify: m <= 32; locate: 2 <= m <= 32, k <= 32
+};
+
 // single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
 // syndrome tests every data shard as the culprit
 struct LocateArgs {
@@ -475,6 +492,8 @@ hipError_t launch_encode_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_encode_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
+hipError_t launch_verify_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
+hipError_t launch_locate_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);

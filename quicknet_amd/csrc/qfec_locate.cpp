@@ -42,7 +42,7 @@ void ratio_rows(const uint8_t* rows, int S, int k, std::vector<uint8_t>& out) {
 
 // perm tables of r_{j,i} = P[j][i] / P[0][i] of `c` on device `dev` (caller holds c->mu; the code
 // passed locate_code_check)
-static int ensure_loc(qfec_code* c, int dev, uint32_t** out) {
+int ensure_loc(qfec_code* c, int dev, uint32_t** out) {
     DevTables& d = c->dev[dev];
     if (d.loc_version != c->version || !d.d_loc) {
         std::vector<uint8_t> r;

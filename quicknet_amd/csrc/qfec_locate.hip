@@ -25,21 +25,10 @@
 
 namespace qfec {
 
-__device__ __forceinline__ bool same16(const uint4& a, const uint4& b) {
-    return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) == 0;
-}
+// same16, nonzero16 and ratio_holds are in qfec_device.hpp, shared with qfec_integrity_ptrs.hip
 
 __device__ __forceinline__ uint4 syndrome16(const uint4& acc, const uint4& p, const uint4& mk) {
     return make_uint4((acc.x ^ p.x) & mk.x, (acc.y ^ p.y) & mk.y, (acc.z ^ p.z) & mk.z, (acc.w ^ p.w) & mk.w);
-}
-
-__device__ __forceinline__ bool nonzero16(const uint4& s) { return (s.x | s.y | s.z | s.w) != 0; }
-
-// r x s0 over 16 bytes == sj ?  (both are zero in the masked bytes)
-__device__ __forceinline__ bool ratio_holds(const Sel (&s0)[4], const uint4& sj, const uint32_t* __restrict__ r) {
-    uint4 pr = make_uint4(0, 0, 0, 0);
-    gf_mac16(pr, s0, r);
-    return same16(pr, sj);
 }
 
 // compile-time K, M

@@ -18,6 +18,8 @@
 //                      built on the device, any k + m), qfec_plan_build_host
 //   qfec_plan_ptrs.cpp qfec_plan_apply_ptrs, qfec_reconstruct_ptrs_wide / qfec_repair_ptrs_wide (the plans applied to
 //                      shards given as a device table of addresses)
+//   qfec_integrity_ptrs.cpp  qfec_verify_ptrs, qfec_locate_ptrs, qfec_scrub_ptrs (the parity check and single-shard
+//                      error location on shards given as a device table of addresses)
 //   qfec_check.cpp     qfec_check_build / qfec_check_apply, qfec_locate_wide / qfec_scrub_wide (check plans built
 //                      on the device: single-shard error location at any k + m), qfec_check_build_host
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
@@ -308,12 +310,19 @@ int run_wide_ptrs(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const ui
 // Can single-shard location work on this code at all?  Decided on the host, before any device.
 // need_lut: also the width of a LUT keyed by the whole mask.
 int locate_code_check(const qfec_code* c, const char* who, bool need_lut);
+// perm tables of r_{j,i} = P[j][i] / P[0][i] of `c` on device `dev` (caller holds c->mu; the code passed
+// locate_code_check)
+int ensure_loc(qfec_code* c, int dev, uint32_t** out);
 // out[i * (S - 1) + (x - 1)] = rows[x][i] / rows[0][i], x = 1..S-1 (0 where rows[0][i] is 0); rows is S x k
 void ratio_rows(const uint8_t* rows, int S, int k, std::vector<uint8_t>& out);
 // the launches of one qfec_locate (validated arguments): two presets, the main kernel per chunk, the
 // finish kernel
 int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_parity, long long groups,
                int block_size, long long pitch, int* d_culprit, uint8_t* d_marks, unsigned* d_counts, hipStream_t s);
+// the same on a pointer table (qfec_integrity_ptrs.cpp): dptrs / pptrs as for run_encode_ptrs, d_marks in the
+// table's own order
+int run_locate_ptrs(DevCtx& ctx, qfec_code* code, const uint64_t* dptrs, const uint64_t* pptrs, long long groups,
+                    int block_size, int* d_culprit, uint8_t* d_marks, unsigned* d_counts, hipStream_t s);
 // locate(marks, extra), then qfec_repair with the marks it wrote; both from stream-ordered scratch
 // (`extra` bytes follow the marks)
 int run_scrub(const char* who, qfec_code* code, uint8_t* d_data, uint8_t* d_parity, long long groups, int block_size,
