@@ -359,6 +359,64 @@ int qfec_repair_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
                           const unsigned char *d_marks, long long groups, int block_size,
                           unsigned int *d_failed, void *stream);
 
+/* The plan calls on pointer tables where every shard has its OWN LENGTH: reconstruct AND repair of
+ * ragged packets where they lie, at any k + m.  d_shards and d_marks are those of
+ * qfec_reconstruct_ptrs_wide (rs.c shard order, any alignment, no pitch, read-only shards may alias);
+ * d_lens (groups * k ints, table order), d_group_len (groups ints: the length of each group's parity
+ * shards) and max_len >= 1 are those of qfec_reconstruct_ptrs_var; d_plan is a plan of either mode
+ * from qfec_plan_build, 16-byte aligned.  Codes: those the plan calls accept, any k + m up to 256,
+ * narrow codes included; QFEC_EUNSUP only for an edited reed_solomon handle.  Asynchronous on
+ * `stream`, no read-back.
+ *   qfec_plan_apply_ptrs_var, per group g, L = d_group_len[g]:
+ *     The plan's status is looked at first.  Status 2 (failed): the group is untouched, its lengths
+ *       are not judged, and this call counts it nowhere -- the build counted it.
+ *     Then the lengths, for status 0 and 1 alike: the group is invalid when L is outside
+ *       [0, max_len] or an unmarked data shard has len_i outside [0, L] (INT_MIN and INT_MAX
+ *       included).  An invalid group is untouched and *d_invalid gains 1 (device counter, may be
+ *       NULL; accumulated, not reset).
+ *     The apply reads no marks: a data shard is unmarked exactly when its id is not among the
+ *       first t entries of the plan's lost list, which for status 0 and 1 equals the marks the plan
+ *       was built from, in both modes (a status-0 plan has t = 0: every data shard is unmarked).
+ *       The d_lens entry of a listed data shard is not looked at.
+ *     Status 0, or L = 0: untouched, counted nowhere.
+ *     Otherwise the group behaves as qfec_plan_apply_ptrs with block_size = L on the same rows with
+ *       every surviving data shard zero-padded to L: the same survivors, coefficient bytes and stale
+ *       flags (a stale row starts from the destination's previous bytes in [0, L)).  Each of the t
+ *       listed shards, data or parity, has room for L bytes and exactly its bytes [0, L) are
+ *       written.  A surviving data shard i is read in [0, len_i) only, a surviving parity shard in
+ *       [0, L).  A survivor with len_i = 0, and any shard the plan neither reads nor writes, is never
+ *       dereferenced: its table entry may be anything.  No byte at or past len_i of a data survivor
+ *       is read on any path; no byte at or past L of any shard is written.
+ *   Alignment, judged per group on the device on the entries the plan dereferences (the survivors
+ *     of non-zero readable length and the listed shards): when all of them are 16-B aligned the
+ *     group runs 16-byte lanes over its whole columns and the L % 16 tail byte by byte; any other
+ *     group is worked on byte by byte, much slower.
+ *   qfec_reconstruct_ptrs_wide_var / qfec_repair_ptrs_wide_var are qfec_plan_build (mode RECONSTRUCT /
+ *     REPAIR) into stream-ordered scratch followed by qfec_plan_apply_ptrs_var, in chunks of at most
+ *     64 MiB of plans; the scratch is freed on the stream.
+ *   Counters: *d_failed is the build's count and comes from the marks alone (t > m, e greater than
+ *     the surviving parity, a singular group); *d_invalid is the apply's.  A group is never in both.
+ *     This DEVIATES from qfec_reconstruct_ptrs_var, which judges lengths before marks and leaves an
+ *     empty group before it looks at the marks: a group that is both under-determined and badly
+ *     sized counts as failed here and as invalid there, and an under-determined group with L = 0
+ *     counts as failed here and nowhere there.  In every other case the two calls count alike.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in
+ *     qfec_last_error after the call's name: a null code, groups < 0, max_len < 1, with groups > 0 a
+ *     null d_shards, d_lens, d_group_len or d_marks / d_plan, a d_plan that is not 16-byte aligned.
+ *     groups == 0 returns QFEC_OK and launches nothing; a bad argument still wins over that. */
+int qfec_plan_apply_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                             const int *d_lens, const int *d_group_len,
+                             const unsigned char *d_plan, long long groups, int max_len,
+                             unsigned int *d_invalid, void *stream);
+int qfec_reconstruct_ptrs_wide_var(qfec_code *code, unsigned char *const *d_shards,
+                                   const int *d_lens, const int *d_group_len,
+                                   const unsigned char *d_marks, long long groups, int max_len,
+                                   unsigned int *d_failed, unsigned int *d_invalid, void *stream);
+int qfec_repair_ptrs_wide_var(qfec_code *code, unsigned char *const *d_shards,
+                              const int *d_lens, const int *d_group_len,
+                              const unsigned char *d_marks, long long groups, int max_len,
+                              unsigned int *d_failed, unsigned int *d_invalid, void *stream);
+
 /* Does the parity match the data?  Bit j of d_bad_rows[g] is set iff parity row j of group g
  * differs from rows[j] x data[g] (a true GF product) in any byte of [0, block_size); 0 = the group
  * is consistent.  d_bad_rows ([groups], may be NULL) is written for every group; *d_bad_groups

@@ -22,6 +22,7 @@ EXPORTS = {
                "qfec_encode_ptrs_var", "qfec_reconstruct_ptrs_var",
                "qfec_plan_stride", "qfec_plan_build", "qfec_plan_apply", "qfec_reconstruct_wide", "qfec_repair_wide",
                "qfec_plan_build_host", "qfec_plan_apply_ptrs", "qfec_reconstruct_ptrs_wide", "qfec_repair_ptrs_wide",
+               "qfec_plan_apply_ptrs_var", "qfec_reconstruct_ptrs_wide_var", "qfec_repair_ptrs_wide_var",
                "qfec_check_stride", "qfec_check_build", "qfec_check_apply", "qfec_locate_wide", "qfec_scrub_wide",
                "qfec_check_build_host",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
@@ -102,6 +103,9 @@ def lib():
         "qfec_plan_apply_ptrs": (i, [vp, vp, vp, ll, i, vp]),
         "qfec_reconstruct_ptrs_wide": (i, [vp, vp, vp, ll, i, vp, vp]),
         "qfec_repair_ptrs_wide": (i, [vp, vp, vp, ll, i, vp, vp]),
+        "qfec_plan_apply_ptrs_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp]),
+        "qfec_reconstruct_ptrs_wide_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp]),
+        "qfec_repair_ptrs_wide_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp]),
         "qfec_reconstruct_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_repair_wide": (i, [vp, vp, vp, vp, ll, i, ll, vp, vp]),
         "qfec_plan_build_host": (i, [vp, vp, i, vp]),

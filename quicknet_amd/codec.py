@@ -514,6 +514,46 @@ class Code:
         (qfec_repair_ptrs_wide).  Arguments as for reconstruct_ptrs."""
         self._ptrs_wide("qfec_repair_ptrs_wide", ptrs, marks, block_size, failed, stream)
 
+    def plan_apply_ptrs_var(self, ptrs, lens, group_len, plan, max_len, invalid=None, stream=None):
+        """plan_apply_ptrs on shards that each have their own length (qfec_plan_apply_ptrs_var).  ptrs and
+        plan as for plan_apply_ptrs; lens: int32 [G*k] on device (the entries of shards the plan lists as
+        lost are not looked at); group_len: int32 [G] on device, the length of every group's parity
+        shards; invalid: optional device int32/uint32 [1] counter of groups refused for their lengths
+        (accumulates).  Reads no marks."""
+        G = self._ptr_groups("plan_apply_ptrs_var", ptrs)
+        if plan.numel() != G * self.plan_stride():
+            raise QfecError(f"plan_apply_ptrs_var: plan has {plan.numel()} bytes for {G} groups of {self.plan_stride()}")
+        self._int32_count("plan_apply_ptrs_var", "lens", lens, G * self.k)
+        self._int32_count("plan_apply_ptrs_var", "group_len", group_len, G)
+        check(lib().qfec_plan_apply_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                             _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(plan, what="plan"), G,
+                                             int(max_len), _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_plan_apply_ptrs_var")
+
+    def _ptrs_wide_var(self, name, ptrs, lens, group_len, marks, max_len, failed, invalid, stream):
+        G = self._ptr_groups(name[5:], ptrs)
+        if marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"{name[5:]}: {marks.numel()} marks for {G} groups of ({self.k},{self.m})")
+        self._int32_count(name[5:], "lens", lens, G * self.k)
+        self._int32_count(name[5:], "group_len", group_len, G)
+        check(getattr(lib(), name)(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                   _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(marks, what="marks"), G,
+                                   int(max_len), _dev_ptr(failed, _I32, "failed"), _dev_ptr(invalid, _I32, "invalid"),
+                                   _stream_handle(stream)), name)
+
+    def reconstruct_ptrs_wide_var(self, ptrs, lens, group_len, marks, max_len, failed=None, invalid=None, stream=None):
+        """reconstruct_ptrs_var for any k + m, through device-built plans (qfec_reconstruct_ptrs_wide_var).
+        Arguments as for reconstruct_ptrs_var.  failed counts from the marks alone, invalid from the
+        lengths of the groups the marks let through: a group is never in both."""
+        self._ptrs_wide_var("qfec_reconstruct_ptrs_wide_var", ptrs, lens, group_len, marks, max_len, failed, invalid,
+                            stream)
+
+    def repair_ptrs_wide_var(self, ptrs, lens, group_len, marks, max_len, failed=None, invalid=None, stream=None):
+        """Rewrite every marked shard, data and parity, where it lies, on shards that each have their own
+        length, for any k + m (qfec_repair_ptrs_wide_var).  Arguments as for reconstruct_ptrs_wide_var;
+        every marked shard has room for group_len bytes."""
+        self._ptrs_wide_var("qfec_repair_ptrs_wide_var", ptrs, lens, group_len, marks, max_len, failed, invalid, stream)
+
     def _ptrs_out(self, what, ptrs, out, out_name, counts=None):
         """The checks verify_ptrs / locate_ptrs / scrub_ptrs share -> (G, out): out is the call's
         per-group device int32 [G] result, allocated when not given; counts is checked when given."""

@@ -355,6 +355,15 @@ struct PlanPtrsArgs {
     int k, m;
 };
 
+// the same with per-shard lengths (k_plan_apply_ptrs_var): p with block = max_len and the geometry of
+// max_len, which only sizes the launch; every group cuts its own length inside the kernel (ptrs_var_geom)
+struct PlanPtrsVarArgs {
+    PlanPtrsArgs p;
+    const int32_t* lens;         // [groups][k] lengths of the data shards of this launch's groups
+    const int32_t* group_len;    // [groups] length of the group's parity shards
+    unsigned int* invalid;       // counter of groups refused for their lengths; may be NULL
+};
+
 // device-built check plans (qfec_check.hip; layout and arithmetic in qfec_plan.hpp): single-shard
 // error location at any k + m.  k_check_build takes a PlanBuildArgs (dmarks NULL: nothing marked;
 // mode, quirk and failed unused; lds = QFEC_PLAN_GF_BYTES + check_work_bytes(k, m)).
@@ -504,6 +513,7 @@ hipError_t launch_locate_erased_finish(const LocErasedFinishArgs& a, hipStream_t
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream);
+hipError_t launch_plan_apply_ptrs_var(const PlanPtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream);
 hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream);

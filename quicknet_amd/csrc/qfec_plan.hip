@@ -15,6 +15,10 @@
 //
 // k_plan_apply_ptrs: the same column body (plan_column) where the rows are given by a device table of
 // shard addresses (qfec_plan_apply_ptrs), in the mapping of the pointer-table kernels of qfec_ptrs.hip.
+//
+// k_plan_apply_ptrs_var: the same where every data shard has its own length (qfec_plan_apply_ptrs_var),
+// with the lengths, the per-group geometry and the clipped loads of qfec_ptrs_var.hip; a wave whose
+// survivors all reach its columns runs plan_column unchanged, any other plan_column_var.
 #include "qfec_device.hpp"
 #include "qfec_geom.hpp"
 #include "qfec_plan.hpp"
@@ -187,6 +191,196 @@ __global__ void __launch_bounds__(256) k_plan_apply_ptrs(PlanPtrsArgs a, const u
         [&](uint64_t b) { plan_column<false>(pw, PL, t256, k, n, t, row, b); });
 }
 
+// plan_column where survivor s may be read in [0, eff(s)) only and counts as zero from there on
+// (qfec_plan_apply_ptrs_var): the same passes of PCH rows, the same scalar reads of the plan.  VEC16:
+// a survivor's 16 bytes at `off` come through ldv_clip -- the whole column, its first bytes in pieces
+// of 8, 4, 2 and 1, or nothing and then no load; else byte `off`, read when it lies below eff(s).  The
+// listed rows are whole in [0, L) and `off` lies inside it: the stale loads and the stores are
+// plan_column's.
+template <bool VEC16, class Row, class Eff>
+__device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL, cptr32 t256, int k, int n, int t,
+                                                const Row& row, const Eff& eff, uint32_t off) {
+    using Acc = typename std::conditional<VEC16, uint4, uint32_t>::type;
+
+    for (int j0 = 0; j0 < t; j0 += PCH) {
+        Acc acc[PCH];
+#pragma unroll
+        for (int j = 0; j < PCH; ++j) {
+            const int jj = j0 + j;
+            const bool stale = jj < t && plan_u8(pw, PL.stale_off + jj) != 0;
+            if constexpr (VEC16) {
+                acc[j] = make_uint4(0, 0, 0, 0);
+                if (stale) acc[j] = *reinterpret_cast<const uint4*>(row(plan_u8(pw, PL.lost_off + jj)) + off);
+            } else {
+                acc[j] = 0;
+                if (stale) acc[j] = row(plan_u8(pw, PL.lost_off + jj))[off];
+            }
+        }
+        for (int c = 0; c < k; ++c) {
+            const uint32_t s = plan_u8(pw, PL.surv_off + c);
+            if (s >= (uint32_t)n) return;  // not a plan of this code
+            const uint8_t* src = row(s);
+            const uint32_t len = eff(s);
+            if constexpr (VEC16) {
+                uint32_t x[4];
+                ldv_clip<4>(x, src, off, len);
+                Sel sl[4];
+                sel16(sl, make_uint4(x[0], x[1], x[2], x[3]));
+#pragma unroll
+                for (int j = 0; j < PCH; ++j)
+                    if (j0 + j < t) {
+                        const cptr32 tc = t256 + plan_u8(pw, PL.coef_off + (j0 + j) * k + c) * QFEC_TAB_STRIDE;
+                        const uint32_t t0 = tc[0], t1 = tc[1], t2 = tc[2], t3 = tc[3], t4 = tc[4];
+                        acc[j].x = xor3(acc[j].x, pp0(sl[0], t0, t1), pp1(sl[0], t2, t3)) ^ pp2(sl[0], t4);
+                        acc[j].y = xor3(acc[j].y, pp0(sl[1], t0, t1), pp1(sl[1], t2, t3)) ^ pp2(sl[1], t4);
+                        acc[j].z = xor3(acc[j].z, pp0(sl[2], t0, t1), pp1(sl[2], t2, t3)) ^ pp2(sl[2], t4);
+                        acc[j].w = xor3(acc[j].w, pp0(sl[3], t0, t1), pp1(sl[3], t2, t3)) ^ pp2(sl[3], t4);
+                    }
+            } else {
+                const Sel sl = gf_sel(off < len ? (uint32_t)src[off] : 0u);
+#pragma unroll
+                for (int j = 0; j < PCH; ++j)
+                    if (j0 + j < t) {
+                        const cptr32 tc = t256 + plan_u8(pw, PL.coef_off + (j0 + j) * k + c) * QFEC_TAB_STRIDE;
+                        acc[j] ^= gf_mul4(sl, tc[0], tc[1], tc[2], tc[3], tc[4]);
+                    }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PCH; ++j)
+            if (j0 + j < t) {
+                const uint32_t l = plan_u8(pw, PL.lost_off + j0 + j);
+                if (l >= (uint32_t)n) continue;
+                if constexpr (VEC16) st16(row(l) + off, acc[j]);
+                else row(l)[off] = (uint8_t)acc[j];
+            }
+    }
+}
+
+// register s >> 6 of the lane s & 63: entry s of the group's table (s wave-uniform, below 64 * NP)
+template <int NP>
+__device__ __forceinline__ uint64_t entry_of(const uint64_t (&p)[NP], uint32_t s) {
+    const uint32_t l = s & 63u, r = s >> 6;
+    if constexpr (NP == 1) return lane_value(p[0], l);
+    else if constexpr (NP == 2) return r == 0 ? lane_value(p[0], l) : lane_value(p[1], l);
+    else
+        return r == 0 ? lane_value(p[0], l) : r == 1 ? lane_value(p[1], l) : r == 2 ? lane_value(p[2], l) : lane_value(p[3], l);
+}
+template <int NP>
+__device__ __forceinline__ uint32_t entry_of(const uint32_t (&v)[NP], uint32_t s) {
+    const uint32_t l = s & 63u, r = s >> 6;
+    if constexpr (NP == 1) return lane_value32(v[0], l);
+    else if constexpr (NP == 2) return r == 0 ? lane_value32(v[0], l) : lane_value32(v[1], l);
+    else
+        return r == 0   ? lane_value32(v[0], l)
+               : r == 1 ? lane_value32(v[1], l)
+               : r == 2 ? lane_value32(v[2], l)
+                        : lane_value32(v[3], l);
+}
+
+// k_plan_apply_ptrs where every data shard has its own length (qfec_plan_apply_ptrs_var): data shard
+// i of a group is len_i bytes and counts as zero-filled up to the group's length L = glen[g], the
+// length of its parity shards.  Mapping and address loads are k_plan_apply_ptrs's, the launch has
+// ptrs_geom(max_len, 16).wpg waves per group.  New here:
+//
+// Lengths.  Lane q * 64 + lane < k loads its length in the same round trip as its address; with L, a
+// scalar load, that makes NP registers of readable length eff (len_i of a data shard, L of a parity
+// shard), read where they are used with readlane, like the addresses.  Every lane executes these
+// loads before the first lane-dependent branch; the early exits are wave-uniform: past the last
+// group, the plan's status, an invalid group, an empty one, a slab at or past L.
+//
+// No marks are read.  A shard is lost when its id is among the first t entries of the plan's lost
+// list, and a data shard that is not lost is a survivor (plan_group lists all of them); the parity
+// survivors are the last e entries of the survivor list.  Lengths are judged after the status: L
+// outside [0, max_len] or a surviving data shard outside [0, L] makes the group invalid, counted by
+// slab 0, lane 0 and untouched.  The length of a lost data shard is not looked at.
+//
+// The group cuts its own geometry, ptrs_var_geom(L, 16).  Alignment is judged on the entries the plan
+// dereferences: the survivors with eff > 0 and the lost rows.  A wave all of whose survivors reach
+// slab_reach<16> runs plan_column<true> unchanged (with all lengths equal: every wave); any other
+// wave runs plan_column_var<true>.  The tail of an aligned group and every byte of a misaligned one
+// run plan_column_var<false>.
+template <int NP>
+__global__ void __launch_bounds__(256) k_plan_apply_ptrs_var(PlanPtrsVarArgs a, const uint64_t* __restrict__ dptrs,
+                                                             const uint64_t* __restrict__ pptrs,
+                                                             const int32_t* __restrict__ lens,
+                                                             const int32_t* __restrict__ glen,
+                                                             const uint8_t* __restrict__ plan) {
+    const int lane = threadIdx.x & 63;
+    uint64_t g;
+    uint32_t slab;
+    if (!wave_item(a.p, &g, &slab)) return;
+    const int k = a.p.k, m = a.p.m, n = k + m;
+    uint64_t p[NP];
+    uint32_t eff[NP];  // as unsigned: a negative length is above every L
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        p[q] = 0;
+        eff[q] = 0;
+        if (i < k) {
+            p[q] = dptrs[g * (uint64_t)k + i];
+            eff[q] = (uint32_t)lens[g * (uint64_t)k + i];
+        } else if (i < n) {
+            p[q] = pptrs[g * (uint64_t)m + (i - k)];
+        }
+    }
+    const uint32_t L = (uint32_t)glen[g];
+    const PlanLayout PL = plan_layout(k, m);
+    const cptr32 pw = (cptr32)(plan + g * a.p.stride);
+    const cptr32 t256 = (cptr32)a.p.t256;
+    const int t = (int)(pw[0] & 0xFFFFu), e = (int)(pw[0] >> 16);
+    const uint32_t status = pw[1] & 0xFFu;
+    if (status > (uint32_t)QFEC_PLAN_WORK || t > m || e > t || e > k) return;  // failed, or not a plan: wave-uniform
+    // which of its entries the plan writes (lost) and reads (used), per lane
+    bool lost[NP], used[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) lost[q] = false;
+    for (int j = 0; j < t; ++j) {
+        const uint32_t l = plan_u8(pw, PL.lost_off + j);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) lost[q] |= l == (uint32_t)(q * 64 + lane);
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        used[q] = i < k && !lost[q];
+        if (i >= k && i < n) eff[q] = L;
+    }
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) bad |= used[q] && eff[q] > L;
+    if (L > a.p.block || __ballot(bad)) {  // invalid: untouched, counted once
+        if (slab == 0 && lane == 0 && a.invalid) atomicAdd(a.invalid, 1u);
+        return;
+    }
+    const PtrsVarGeom v = ptrs_var_geom(L, 16);
+    if (status != (uint32_t)QFEC_PLAN_WORK || slab >= v.live) return;  // nothing to do, an empty group, a slab at or past L
+    for (int r = 0; r < e; ++r) {
+        const uint32_t s = plan_u8(pw, PL.surv_off + k - e + r);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) used[q] |= s == (uint32_t)(q * 64 + lane);
+    }
+    const uint32_t reach = slab_reach<16>(v, slab);
+    bool low = false, cut = false;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        low |= ((used[q] && eff[q] != 0) || lost[q]) && ((uint32_t)p[q] & 15u) != 0;
+        cut |= used[q] && eff[q] < reach;
+    }
+    const bool aligned = __ballot(low) == 0;
+    const bool full = __ballot(cut) == 0;
+    auto row = [&](uint32_t s) -> uint8_t* { return as_out(entry_of<NP>(p, s)); };
+    auto len_of = [&](uint32_t s) -> uint32_t { return entry_of<NP>(eff, s); };
+    run_slab_var<16>(
+        v, L, slab, lane, aligned,
+        [&](uint32_t off) {
+            if (full) plan_column<true>(pw, PL, t256, k, n, t, row, (uint64_t)off);
+            else plan_column_var<true>(pw, PL, t256, k, n, t, row, len_of, off);
+        },
+        [&](uint32_t b) { plan_column_var<false>(pw, PL, t256, k, n, t, row, len_of, b); });
+}
+
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream) {
     if (a.groups == 0) return hipSuccess;
     if (a.groups > 0x7FFFFFFFull / 64u || a.lds > 65536u) return hipErrorInvalidValue;  // caller chunks
@@ -213,6 +407,25 @@ hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream) {
     if (n <= 64) hipLaunchKernelGGL((k_plan_apply_ptrs<1>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
     else if (n <= 128) hipLaunchKernelGGL((k_plan_apply_ptrs<2>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
     else hipLaunchKernelGGL((k_plan_apply_ptrs<4>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_plan_apply_ptrs_var(const PlanPtrsVarArgs& a, hipStream_t stream) {
+    if (a.p.groups == 0) return hipSuccess;
+    const uint64_t waves = a.p.groups * (uint64_t)a.p.wpg;
+    const int n = a.p.k + a.p.m;
+    if (a.p.wpg != ptrs_geom((int)a.p.block, 16).wpg || waves * 64u > (uint64_t)kMaxLaunchLanes || n > 256)
+        return hipErrorInvalidValue;  // caller chunks
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (n <= 64)
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var<1>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.plan);
+    else if (n <= 128)
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var<2>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.plan);
+    else
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var<4>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.plan);
     return hipGetLastError();
 }
 

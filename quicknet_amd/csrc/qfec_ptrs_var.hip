@@ -45,57 +45,7 @@
 
 namespace qfec {
 
-// v of lane l; l is wave-uniform
-__device__ __forceinline__ uint32_t lane_value32(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-
-// the first n < 4 D bytes at q, zero after them: a piece of 8, 4, 2 and 1 bytes per set bit of n, each
-// at the offset the larger pieces leave, which its own size divides (q is 4 D-aligned: the group is
-// aligned).  Never a byte at or past n.
-template <int D>
-__device__ __forceinline__ void ldv_part(uint32_t (&v)[D], const uint8_t* q, uint32_t n) {
-    static_assert(D == 4 || D == 2, "16-B or 8-B lanes");
-    constexpr uint32_t W = 4u * D;
-    uint64_t lo = 0, hi = 0;
-    if constexpr (D == 4) {
-        if (n & 8u) lo = *reinterpret_cast<const uint64_t*>(q);
-    }
-    if (n & 4u) {
-        const uint32_t p = n & (W - 1u) & 8u;
-        const uint64_t w = *reinterpret_cast<const uint32_t*>(q + p);
-        if (p) hi |= w;
-        else lo |= w;
-    }
-    if (n & 2u) {
-        const uint32_t p = n & (W - 1u) & 12u;
-        const uint64_t w = (uint64_t)*reinterpret_cast<const uint16_t*>(q + p) << (8u * (p & 7u));
-        if (p & 8u) hi |= w;
-        else lo |= w;
-    }
-    if (n & 1u) {
-        const uint32_t p = n & (W - 1u) & 14u;
-        const uint64_t w = (uint64_t)q[p] << (8u * (p & 7u));
-        if (p & 8u) hi |= w;
-        else lo |= w;
-    }
-    v[0] = (uint32_t)lo;
-    v[1] = (uint32_t)(lo >> 32);
-    if constexpr (D == 4) {
-        v[2] = (uint32_t)hi;
-        v[3] = (uint32_t)(hi >> 32);
-    }
-}
-
-// D dwords of a row of `len` bytes at byte `off`, zero past len.  The whole column: ldv.  Nothing
-// of it: no load.  Part of it: ldv_part.  One branch per source: the form of the runtime-k,m kernels.
-template <int D>
-__device__ __forceinline__ void ldv_clip(uint32_t (&v)[D], const uint8_t* row, uint32_t off, uint32_t len) {
-    if (off + 4u * D <= len) ldv<D>(v, row + off);
-    else ldv_part<D>(v, row + off, len > off ? len - off : 0u);
-}
-
-// The same for the templated bodies, without a branch per source.  A lane whose column is not whole
+// ldv_clip of qfec_ptrs_device.hpp for the templated bodies, without a branch per source.  A lane whose column is not whole
 // in this row loads the column of `safe` instead, a row of the group that is whole wherever a lane
 // works (the group's longest data shard, a parity survivor), and drops it: the loads issue together
 // as in the fixed-length body and no byte at or past len is read.  The row's part column was loaded
@@ -155,30 +105,6 @@ __device__ __forceinline__ uint4 ld16_ragged(const uint8_t* row, const uint8_t* 
     uint32_t v[4];
     ldv_ragged<4>(v, row, safe, off, len, part, s);
     return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-// A wave's share of a group of length len.  vec(off): the lane's whole column of W bytes at byte
-// off; byte(b): byte b.  Every access lies inside [0, len): a column ends at vcols * W <= len, the
-// tail at tail0 + tailn = len, the byte span at min(slab end, len).  The caller has left already
-// when slab >= live.
-template <int W, class Vec, class Byte>
-__device__ __forceinline__ void run_slab_var(const PtrsVarGeom& v, uint32_t len, uint32_t slab, int lane, bool aligned,
-                                             Vec&& vec, Byte&& byte) {
-    if (aligned) {
-        const uint32_t col = slab * 64u + lane;
-        if (col < v.vcols) vec(col * (uint32_t)W);
-        if (slab + 1 == v.live && (uint32_t)lane < v.tailn) byte(v.tail0 + lane);
-    } else {
-        const uint32_t end = std::min((slab + 1) * 64u * W, len);
-#pragma unroll 1
-        for (uint32_t b = slab * 64u * W + lane; b < end; b += 64) byte(b);
-    }
-}
-
-// how far the whole columns of a wave reach: a source at least this long is read by vector loads only
-template <int W>
-__device__ __forceinline__ uint32_t slab_reach(const PtrsVarGeom& v, uint32_t slab) {
-    return std::min((slab + 1) * 64u * W, v.tail0);
 }
 
 // ------------------------------------------------------------------ encode
