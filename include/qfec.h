@@ -580,6 +580,76 @@ int qfec_scrub_ptrs(qfec_code *code, unsigned char *const *d_shards,
                     int *d_culprit /* nullable */, unsigned int *d_counts /* [3], nullable */,
                     unsigned int *d_failed /* nullable, accumulates */, void *stream);
 
+/* The integrity family on pointer tables with per-shard lengths: what a caller of
+ * qfec_encode_ptrs_var asks afterwards -- does this group's parity still match, which packet is
+ * corrupted, put it right -- on the packets where they lie, without a copy into padded slots.
+ *   Arguments: d_shards is qfec_verify_ptrs' table.  d_lens holds groups * k ints in table order, the
+ *     length of every data shard; d_group_len holds groups ints, the length L of each group's parity
+ *     shards: what qfec_encode_ptrs_var reported and what a receiver reads off a parity packet.
+ *     max_len >= 1 only sizes the launch.
+ *   Data shard i of a group counts as zero-filled from len_i up to L.  It is read in [0, len_i) only
+ *     and a parity shard in [0, L) only; no byte at or past those is read on any path and none
+ *     influences a result.  A data shard with len_i == 0 is never dereferenced: its table entry may be
+ *     anything and takes no part in the alignment judgement.
+ *   An invalid group: L outside [0, max_len], or ANY data shard with len_i outside [0, L] (INT_MIN and
+ *     INT_MAX included; all k lengths are judged, there are no marks).  No byte of it is read or
+ *     written and *d_invalid (device counter, may be NULL; accumulated) gains 1, exactly once;
+ *     d_bad_rows[g] = 0, d_culprit[g] = QFEC_LOC_INVALID, its marks are all zero, and it counts nowhere
+ *     in d_counts or *d_bad_groups.  An empty group (L == 0) gives d_bad_rows[g] = 0 and
+ *     QFEC_LOC_CLEAN with nothing dereferenced.
+ *   qfec_verify_ptrs_var: d_bad_rows[g] is what qfec_verify_ptrs with block_size = L gives on the same
+ *     shards with every data shard zero-padded to L (a true GF product, no stale-row quirk).  With
+ *     d_bad_rows, d_bad_groups and d_invalid all NULL the call returns QFEC_OK and launches nothing.
+ *   qfec_locate_ptrs_var: the verdict of qfec_locate_ptrs on the zero-padded rows, with one more
+ *     condition on a data candidate.  A shorter shard is a stricter code: shard i is KNOWN to be zero
+ *     in [len_i, L), so it cannot be wrong there, and it stays a candidate only if every syndrome is
+ *     zero in every byte position >= len_i.  A group whose only padded-rows explanation is a data shard
+ *     "wrong" beyond its own end is therefore QFEC_LOC_MULTI.  d_marks (may be NULL) comes back in the
+ *     table's own order; it may go to qfec_repair_ptrs_wide_var only when the marked shard has room
+ *     for L bytes (that call writes [0, L) of every listed shard) -- qfec_scrub_ptrs_var has no such
+ *     condition.  d_counts and the m = 2 caveat are those of qfec_locate.
+ *   qfec_scrub_ptrs_var: the locate into d_culprit (stream-ordered scratch when it is NULL), then one
+ *     correction launch, which needs no plan: one located shard is fixed from one parity row.  A
+ *     located data shard i has exactly its bytes [0, len_i) rewritten as (parity_0 ^ sum_{c != i}
+ *     rows[0][c] x data_c) / rows[0][i], the other data read clipped to their lengths; a located parity
+ *     shard j has exactly [0, L) rewritten as sum_c rows[j][c] x data_c.  No byte at or past len_i of
+ *     a data culprit or past L of a parity culprit is written; CLEAN, MULTI, AMBIGUOUS, INVALID and
+ *     empty groups are untouched byte for byte.  With all lengths equal this is byte for byte what
+ *     qfec_scrub_ptrs writes.  A rewritten shard must not overlap any other shard of the batch.
+ *   Codes: qfec_verify_ptrs_var takes any k with m <= 32.  qfec_locate_ptrs_var and
+ *     qfec_scrub_ptrs_var have qfec_locate's limits (m >= 2, k <= 32, m <= 32, no zero coefficient).
+ *     The scrub has NO k + m <= 24 limit and does not refuse an edited reed_solomon handle: it uses
+ *     only the parity rows the locate judged with.  QFEC_EUNSUP is decided on the host before a device
+ *     is touched.
+ *   Alignment, judged per group on the device on the entries the call may dereference: an aligned
+ *     group runs 16-byte lanes over its whole columns and the L % 16 tail bytes byte by byte; any
+ *     other group is worked on byte by byte, much slower.
+ *   Asynchronous on `stream`: no host synchronisation, no read-back; working words come from
+ *     stream-ordered scratch.  A batch beyond one launch's index space goes in several.
+ *   QFEC_EINVAL, decided on the host first, the cause named in qfec_last_error after the call's name:
+ *     a null code, groups < 0, max_len < 1, with groups > 0 a null d_shards, d_lens or d_group_len,
+ *     and for qfec_locate_ptrs_var a null d_culprit.  groups == 0 returns QFEC_OK and launches
+ *     nothing; a bad argument still wins over that. */
+#define QFEC_LOC_INVALID (-6)   /* the group's lengths are out of range: nothing of it was read */
+
+int qfec_verify_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                         const int *d_lens, const int *d_group_len,
+                         long long groups, int max_len,
+                         unsigned int *d_bad_rows   /* [groups], nullable */,
+                         unsigned int *d_bad_groups /* counter, accumulates, nullable */,
+                         unsigned int *d_invalid    /* counter, accumulates, nullable */, void *stream);
+int qfec_locate_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                         const int *d_lens, const int *d_group_len,
+                         long long groups, int max_len,
+                         int *d_culprit, unsigned char *d_marks /* nullable */,
+                         unsigned int *d_counts /* [3], nullable */,
+                         unsigned int *d_invalid /* nullable */, void *stream);
+int qfec_scrub_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                        const int *d_lens, const int *d_group_len,
+                        long long groups, int max_len,
+                        int *d_culprit /* nullable */, unsigned int *d_counts /* [3], nullable */,
+                        unsigned int *d_invalid /* nullable */, void *stream);
+
 /* Which TWO shards are wrong?  qfec_locate stops at one corrupted shard per group and calls the rest
  * MULTI.  A code with m >= 4 parity rows has minimum distance m + 1 >= 5 and determines two corrupted
  * shards uniquely.  With H = [rows | I_m], h_x = column x of the parity rows for a data shard x < k

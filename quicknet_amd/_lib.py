@@ -27,6 +27,7 @@ EXPORTS = {
                "qfec_check_build_host",
                "qfec_locate", "qfec_scrub", "qfec_locate_ratios",
                "qfec_verify_ptrs", "qfec_locate_ptrs", "qfec_scrub_ptrs",
+               "qfec_verify_ptrs_var", "qfec_locate_ptrs_var", "qfec_scrub_ptrs_var",
                "qfec_locate2", "qfec_scrub2", "qfec_locate2_checks",
                "qfec_locate_erased", "qfec_prepare_locate_erased", "qfec_scrub_erased", "qfec_locate_erased_plan",
                "qfec_pipe_new", "qfec_pipe_free", "qfec_pipe_encode", "qfec_pipe_reconstruct", "qfec_pipe_wait", "qfec_pipe_slots",
@@ -47,6 +48,7 @@ QFEC_VARIANT_PERM = 0
 QFEC_VARIANT_LDSLOG = 1
 QFEC_LOC_CLEAN, QFEC_LOC_MULTI, QFEC_LOC_AMBIGUOUS = -1, -2, -3  # qfec_locate verdicts (include/qfec.h)
 QFEC_LOC_UNCHECKED, QFEC_LOC_LOST = -4, -5  # qfec_locate_erased: no spare row to check with; under-determined
+QFEC_LOC_INVALID = -6  # the calls with per-shard lengths: the group's lengths are out of range
 QFEC_UPD_NONE = -1  # qfec_update: this group is untouched
 QFEC_PLAN_RECONSTRUCT, QFEC_PLAN_REPAIR = 0, 1  # qfec_plan_build modes
 
@@ -121,6 +123,9 @@ def lib():
         "qfec_verify_ptrs": (i, [vp, vp, ll, i, vp, vp, vp]),
         "qfec_locate_ptrs": (i, [vp, vp, ll, i, vp, vp, vp, vp]),
         "qfec_scrub_ptrs": (i, [vp, vp, ll, i, vp, vp, vp, vp]),
+        "qfec_verify_ptrs_var": (i, [vp, vp, vp, vp, ll, i, vp, vp, vp, vp]),
+        "qfec_locate_ptrs_var": (i, [vp, vp, vp, vp, ll, i, vp, vp, vp, vp, vp]),
+        "qfec_scrub_ptrs_var": (i, [vp, vp, vp, vp, ll, i, vp, vp, vp, vp]),
         "qfec_locate2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub2": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate2_checks": (i, [vp, i, i, vp]),

@@ -14,7 +14,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import QFEC_CAUCHY, QFEC_VANDERMONDE, RSStruct, QfecError, check, lib
+from ._lib import QFEC_CAUCHY, QFEC_LOC_INVALID, QFEC_VANDERMONDE, RSStruct, QfecError, check, lib
+
+LOC_INVALID = QFEC_LOC_INVALID  # verify / locate / scrub _ptrs_var: a group refused for its lengths
 
 __all__ = ["Code", "FecParms", "ReedSolomon", "QfecError", "QFEC_CAUCHY", "QFEC_VANDERMONDE",
            "set_kernel_variant", "tune", "synth_fill", "probe_stream", "probe_reconstruct", "rs_host_devices", "device_count", "frame_udp", "unframe_udp",
@@ -604,6 +606,59 @@ class Code:
         check(lib().qfec_scrub_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
                                     _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
                                     _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_scrub_ptrs")
+        return culprit
+
+    def _ptrs_var_out(self, what, ptrs, lens, group_len, out, out_name, counts=None):
+        """_ptrs_out plus the count and dtype checks of lens [G*k] and group_len [G]."""
+        G, out = self._ptrs_out(what, ptrs, out, out_name, counts)
+        self._int32_count(what, "lens", lens, G * self.k)
+        self._int32_count(what, "group_len", group_len, G)
+        return G, out
+
+    def verify_ptrs_var(self, ptrs, lens, group_len, max_len, bad_rows=None, bad_groups=None, invalid=None, stream=None):
+        """verify_ptrs() on shards that each have their own length (qfec_verify_ptrs_var).  ptrs as for
+        encode_ptrs; lens: int32 [G*k] on device, the length of every data shard in table order;
+        group_len: int32 [G] on device, the length of every group's parity shards, as encode_ptrs_var
+        reported it; max_len: the longest length any group may have.  A data shard counts as
+        zero-filled up to its group's length and is read below its own length only.  Returns bad_rows
+        (0 for a group refused for its lengths); bad_groups / invalid: optional device int32/uint32 [1]
+        counters of inconsistent groups / of groups refused for their lengths (accumulate)."""
+        G, bad_rows = self._ptrs_var_out("verify_ptrs_var", ptrs, lens, group_len, bad_rows, "bad_rows")
+        check(lib().qfec_verify_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                         _dev_ptr(group_len, _I32, "group_len"), G, int(max_len),
+                                         _dev_ptr(bad_rows, _I32, "bad_rows"), _dev_ptr(bad_groups, _I32, "bad_groups"),
+                                         _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_verify_ptrs_var")
+        return bad_rows
+
+    def locate_ptrs_var(self, ptrs, lens, group_len, max_len, culprit=None, marks=None, counts=None, invalid=None,
+                        stream=None):
+        """locate_ptrs() on shards that each have their own length (qfec_locate_ptrs_var).  Arguments
+        as for verify_ptrs_var.  Returns culprit as locate() does, with LOC_INVALID for a group refused
+        for its lengths; a data shard is a candidate only if every syndrome is zero from its own end
+        on.  marks as for locate_ptrs(): ready for repair_ptrs_wide_var() only where the marked shard
+        has room for group_len bytes; scrub_ptrs_var() has no such condition."""
+        G, culprit = self._ptrs_var_out("locate_ptrs_var", ptrs, lens, group_len, culprit, "culprit", counts)
+        if marks is not None and marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"locate_ptrs_var: marks has {marks.numel()} elements for {G} groups of {self.k + self.m}")
+        check(lib().qfec_locate_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                         _dev_ptr(group_len, _I32, "group_len"), G, int(max_len),
+                                         _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks, what="marks"),
+                                         _dev_ptr(counts, _I32, "counts"), _dev_ptr(invalid, _I32, "invalid"),
+                                         _stream_handle(stream)), "qfec_locate_ptrs_var")
+        return culprit
+
+    def scrub_ptrs_var(self, ptrs, lens, group_len, max_len, culprit=None, counts=None, invalid=None, stream=None):
+        """locate_ptrs_var() and the correction of the located shard in one call (qfec_scrub_ptrs_var): a
+        located data shard has exactly its own length rewritten, a located parity shard group_len
+        bytes; every other group is left as it is.  No plan is built, so any code locate() takes is
+        accepted.  Returns culprit as locate_ptrs_var() does."""
+        G, culprit = self._ptrs_var_out("scrub_ptrs_var", ptrs, lens, group_len, culprit, "culprit", counts)
+        check(lib().qfec_scrub_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                        _dev_ptr(group_len, _I32, "group_len"), G, int(max_len),
+                                        _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
+                                        _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_scrub_ptrs_var")
         return culprit
 
     def plan_host(self, marks_n, mode):

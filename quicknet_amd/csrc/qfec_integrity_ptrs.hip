@@ -40,106 +40,6 @@
 
 namespace qfec {
 
-__device__ __forceinline__ void xor16(uint4& a, const uint4& b) {
-    a.x ^= b.x;
-    a.y ^= b.y;
-    a.z ^= b.z;
-    a.w ^= b.w;
-}
-
-// Byte b of the group: its m syndromes s_r = parity_r ^ sum_c P[r][c] x data_c, row(s) = the address
-// of shard s.  The non-zero rows are OR-ed into `bad`.  LOC: a data shard i stays in `cand` while
-// s_r == r_{r,i} x s_0 holds in every row r >= 1 tested; rows are tested from the byte's first
-// non-zero syndrome on (a row skipped before it is zero beside a zero s_0, which every candidate
-// explains).  K > 0 (k == K): the K input bytes are loaded at once, as in encode_byte; the rows stay
-// a rolled loop.
-template <int K, bool LOC, class Row>
-__device__ __forceinline__ void check_byte(int k, int m, const uint32_t* tab, const uint32_t* rtab, const Row& row,
-                                           uint64_t b, uint32_t& bad, uint32_t& cand) {
-    uint32_t x[K > 0 ? K : 1];
-    if constexpr (K > 0) {
-#pragma unroll
-        for (int c = 0; c < K; ++c) x[c] = as_row(row(c))[b];
-    }
-    uint32_t here = 0;
-    Sel s0 = gf_sel(0u);
-#pragma unroll 1
-    for (int r = 0; r < m; ++r) {
-        const uint32_t* tr = tab + (r * k) * QFEC_TAB_STRIDE;
-        uint32_t s = as_row(row(k + r))[b];
-        if constexpr (K > 0) {
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
-                s ^= gf_mul4(gf_sel(x[c]), tc[0], tc[1], tc[2], tc[3], tc[4]);
-            }
-        } else {
-            for (int c = 0; c < k; ++c) {
-                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
-                s ^= gf_mul4(gf_sel((uint32_t)as_row(row(c))[b]), tc[0], tc[1], tc[2], tc[3], tc[4]);
-            }
-        }
-        s &= 0xFFu;
-        if (s) here |= 1u << r;
-        if constexpr (LOC) {
-            if (r == 0) {
-                s0 = gf_sel(s);
-            } else if (here != 0) {
-#pragma unroll 1
-                for (int i = 0; i < k; ++i) {
-                    const uint32_t* tc = rtab + (i * (m - 1) + r - 1) * QFEC_TAB_STRIDE;
-                    if ((gf_mul4(s0, tc[0], tc[1], tc[2], tc[3], tc[4]) & 0xFFu) != s) cand &= ~(1u << i);
-                }
-            }
-        }
-    }
-    bad |= here;
-}
-
-// the M syndromes of the whole column at byte `off`; p: the lanes' addresses.  Parity first, then
-// the data (products16's comment has the register effect of that order); K >= 16 in two halves with
-// encode_column's barrier.
-template <int K, int M>
-__device__ __forceinline__ void syndromes16(uint4 (&s)[M], uint64_t p, const uint32_t* tab, uint64_t off) {
-    uint4 par[M];
-#pragma unroll
-    for (int r = 0; r < M; ++r) par[r] = ld16(as_row(lane_value(p, K + r)) + off);
-#pragma unroll
-    for (int r = 0; r < M; ++r) s[r] = make_uint4(0, 0, 0, 0);
-    if constexpr (K >= 16) {
-        constexpr int H = (K + 1) / 2;
-        {
-            uint4 x[H];
-#pragma unroll
-            for (int c = 0; c < H; ++c) x[c] = ld16(as_row(lane_value(p, c)) + off);
-            enc_mac16<K, M, 0, H>(s, x, tab);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
-        {
-            uint4 x[K - H];
-#pragma unroll
-            for (int c = 0; c < K - H; ++c) x[c] = ld16(as_row(lane_value(p, H + c)) + off);
-            enc_mac16<K, M, H, K - H>(s, x, tab);
-        }
-    } else {
-        uint4 x[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) x[c] = ld16(as_row(lane_value(p, c)) + off);
-        enc_mac16<K, M, 0, K>(s, x, tab);
-    }
-#pragma unroll
-    for (int r = 0; r < M; ++r) xor16(s[r], par[r]);
-}
-
-// lane s < k + m: the address of shard s of group g; the rest zero
-__device__ __forceinline__ uint64_t lane_row(const uint64_t* __restrict__ dptrs, const uint64_t* __restrict__ pptrs,
-                                             uint64_t g, int k, int m, int lane) {
-    uint64_t p = 0;
-    if (lane < k) p = dptrs[g * (uint64_t)k + lane];
-    else if (lane < k + m) p = pptrs[g * (uint64_t)m + (lane - k)];
-    return p;
-}
-
 // ------------------------------------------------------------------ verify
 
 // __restrict__ parameters: nothing the launch reads through them is written by it

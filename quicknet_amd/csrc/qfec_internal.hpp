@@ -199,6 +199,25 @@ struct IntegrityPtrsArgs {
     int k, m;                 // verify: m <= 32; locate: 2 <= m <= 32, k <= 32
 };
 
+// the same with per-shard lengths (qfec_integrity_ptrs_var.hip): p with block = max_len and the geometry
+// of max_len, which only sizes the launch; every group cuts its own length inside the kernel (ptrs_var_geom)
+struct IntegrityPtrsVarArgs {
+    IntegrityPtrsArgs p;
+    const int32_t* lens;         // [groups][k] lengths of the data shards of this launch's groups
+    const int32_t* group_len;    // [groups] length of the group's parity shards
+};
+
+// the groups the kernels above left alone for their lengths, one thread per group (k_var_invalid)
+struct VarInvalidArgs {
+    const int32_t* lens;         // [groups][k]
+    const int32_t* group_len;    // [groups]
+    int* culprit;                // [groups]: QFEC_LOC_INVALID written for an invalid group; may be NULL
+    unsigned int* invalid;       // counter of invalid groups; may be NULL
+    uint64_t groups;
+    uint32_t max_len;
+    int k;
+};
+
 // single-shard error location (qfec_locate.hip): verify's mapping; a wave that holds a non-zero
 // syndrome tests every data shard as the culprit
 struct LocateArgs {
@@ -503,6 +522,12 @@ hipError_t launch_encode_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_verify_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
 hipError_t launch_locate_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
+hipError_t launch_verify_ptrs_var(const IntegrityPtrsVarArgs& a, hipStream_t stream);
+hipError_t launch_locate_ptrs_var(const IntegrityPtrsVarArgs& a, hipStream_t stream);
+// qfec_scrub_ptrs_var's correction: culprit [groups] of this launch, t256 and exp[512] of the device context
+hipError_t launch_correct_ptrs_var(const IntegrityPtrsVarArgs& a, const int32_t* culprit, const uint32_t* t256,
+                                   const uint8_t* gf_exp, hipStream_t stream);
+hipError_t launch_var_invalid(const VarInvalidArgs& a, hipStream_t stream);
 hipError_t launch_locate(const LocateArgs& a, hipStream_t stream);
 hipError_t launch_locate_finish(const LocateFinishArgs& a, hipStream_t stream);
 hipError_t launch_locate2_list(const Locate2Args& a, hipStream_t stream);

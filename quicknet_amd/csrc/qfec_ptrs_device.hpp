@@ -3,7 +3,9 @@
 // k_plan_apply_ptrs_var): reading an address out of the lane that loaded it, saying that it is global
 // memory, a wave's share of its group's shards, the encode's vector body on row addresses, and for
 // the kernels with per-shard lengths a lane's length, the clipped column load and a wave's share of
-// a group that has its own length.
+// a group that has its own length, the ragged column loads of the templated bodies, and for the integrity
+// kernels (qfec_integrity_ptrs.hip, qfec_integrity_ptrs_var.hip) the syndromes of a byte and of a column
+// on row addresses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -173,6 +175,168 @@ __device__ __forceinline__ void run_slab_var(const PtrsVarGeom& v, uint32_t len,
 template <int W>
 __device__ __forceinline__ uint32_t slab_reach(const PtrsVarGeom& v, uint32_t slab) {
     return std::min((slab + 1) * 64u * W, v.tail0);
+}
+
+// ---------------------------------------------------------------- ragged columns
+// (qfec_ptrs_var.hip, qfec_integrity_ptrs_var.hip: the templated bodies of a wave that is not `full`)
+
+// ldv_clip of qfec_ptrs_device.hpp for the templated bodies, without a branch per source.  A lane whose column is not whole
+// in this row loads the column of `safe` instead, a row of the group that is whole wherever a lane
+// works (the group's longest data shard, a parity survivor), and drops it: the loads issue together
+// as in the fixed-length body and no byte at or past len is read.  The row's part column was loaded
+// before the lanes parted, by the lane that holds the row's address and length (lane_part), so the
+// part columns of all rows cost the wave one round trip, at the same time as the whole columns; the
+// lane whose column it is takes it from lane s with readlane.
+template <int D>
+__device__ __forceinline__ void ldv_ragged(uint32_t (&v)[D], const uint8_t* row, const uint8_t* safe, uint32_t off,
+                                           uint32_t len, const uint32_t (&part)[D], uint32_t s) {
+    constexpr uint32_t W = 4u * D;
+    const bool whole = off + W <= len;
+    ldv<D>(v, (whole ? row : safe) + off);
+    const bool mine = len % W != 0 && off == len / W * W;
+#pragma unroll
+    for (int d = 0; d < D; ++d) v[d] = mine ? lane_value32(part[d], s) : whole ? v[d] : 0u;
+}
+
+// Every lane of a ragged wave calls it before the first lane-dependent branch.  source: the lane
+// holds the address p and the readable length len of a row the wave reads.  A lane whose row's part
+// column lies in this slab loads it: bytes [len / W * W, len) of the row, zero after them.
+template <int D>
+__device__ __forceinline__ void lane_part(uint32_t (&part)[D], bool source, uint64_t p, uint32_t len, uint32_t slab) {
+    constexpr uint32_t W = 4u * D;
+#pragma unroll
+    for (int d = 0; d < D; ++d) part[d] = 0;
+    const uint32_t pc = len / W, pn = len % W;
+    if (source && pn && (pc >> 6) == slab) ldv_part<D>(part, as_row(p) + pc * W, pn);
+}
+
+__device__ __forceinline__ uint4 ld16_clip(const uint8_t* row, uint32_t off, uint32_t len) {
+    uint32_t v[4];
+    ldv_clip<4>(v, row, off, len);
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+__device__ __forceinline__ uint4 ld16_ragged(const uint8_t* row, const uint8_t* safe, uint32_t off, uint32_t len,
+                                             const uint32_t (&part)[4], uint32_t s) {
+    uint32_t v[4];
+    ldv_ragged<4>(v, row, safe, off, len, part, s);
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// Sources per pass of the ragged column bodies: the largest divisor of K up to CAP.  The ragged bodies
+// are loops rolled over the sources in such chunks, not the unrolled bodies of the fixed-length
+// kernels: a kernel's registers are those of its larger path, and unrolled next to the full path the
+// ragged encode of RS(16,4) holds 238 VGPRs (2 waves per SIMD) and the ragged reconstruct 101 (4 waves),
+// where the full paths alone hold 93 and 94.
+template <int K, int CAP>
+constexpr int ragged_chunk() {
+    int best = 1;
+    for (int d = 2; d <= CAP && d <= K; ++d)
+        if (K % d == 0) best = d;
+    return best;
+}
+
+// ---------------------------------------------------------------- syndromes on row addresses
+// (qfec_integrity_ptrs.hip, qfec_integrity_ptrs_var.hip)
+
+__device__ __forceinline__ void xor16(uint4& a, const uint4& b) {
+    a.x ^= b.x;
+    a.y ^= b.y;
+    a.z ^= b.z;
+    a.w ^= b.w;
+}
+
+// Byte b of the group: its m syndromes s_r = parity_r ^ sum_c P[r][c] x data_c, row(s) = the address
+// of shard s.  The non-zero rows are OR-ed into `bad`.  LOC: a data shard i stays in `cand` while
+// s_r == r_{r,i} x s_0 holds in every row r >= 1 tested; rows are tested from the byte's first
+// non-zero syndrome on (a row skipped before it is zero beside a zero s_0, which every candidate
+// explains).  K > 0 (k == K): the K input bytes are loaded at once, as in encode_byte; the rows stay
+// a rolled loop.
+template <int K, bool LOC, class Row>
+__device__ __forceinline__ void check_byte(int k, int m, const uint32_t* tab, const uint32_t* rtab, const Row& row,
+                                           uint64_t b, uint32_t& bad, uint32_t& cand) {
+    uint32_t x[K > 0 ? K : 1];
+    if constexpr (K > 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) x[c] = as_row(row(c))[b];
+    }
+    uint32_t here = 0;
+    Sel s0 = gf_sel(0u);
+#pragma unroll 1
+    for (int r = 0; r < m; ++r) {
+        const uint32_t* tr = tab + (r * k) * QFEC_TAB_STRIDE;
+        uint32_t s = as_row(row(k + r))[b];
+        if constexpr (K > 0) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
+                s ^= gf_mul4(gf_sel(x[c]), tc[0], tc[1], tc[2], tc[3], tc[4]);
+            }
+        } else {
+            for (int c = 0; c < k; ++c) {
+                const uint32_t* tc = tr + c * QFEC_TAB_STRIDE;
+                s ^= gf_mul4(gf_sel((uint32_t)as_row(row(c))[b]), tc[0], tc[1], tc[2], tc[3], tc[4]);
+            }
+        }
+        s &= 0xFFu;
+        if (s) here |= 1u << r;
+        if constexpr (LOC) {
+            if (r == 0) {
+                s0 = gf_sel(s);
+            } else if (here != 0) {
+#pragma unroll 1
+                for (int i = 0; i < k; ++i) {
+                    const uint32_t* tc = rtab + (i * (m - 1) + r - 1) * QFEC_TAB_STRIDE;
+                    if ((gf_mul4(s0, tc[0], tc[1], tc[2], tc[3], tc[4]) & 0xFFu) != s) cand &= ~(1u << i);
+                }
+            }
+        }
+    }
+    bad |= here;
+}
+
+// the M syndromes of the whole column at byte `off`; p: the lanes' addresses.  Parity first, then
+// the data (products16's comment has the register effect of that order); K >= 16 in two halves with
+// encode_column's barrier.
+template <int K, int M>
+__device__ __forceinline__ void syndromes16(uint4 (&s)[M], uint64_t p, const uint32_t* tab, uint64_t off) {
+    uint4 par[M];
+#pragma unroll
+    for (int r = 0; r < M; ++r) par[r] = ld16(as_row(lane_value(p, K + r)) + off);
+#pragma unroll
+    for (int r = 0; r < M; ++r) s[r] = make_uint4(0, 0, 0, 0);
+    if constexpr (K >= 16) {
+        constexpr int H = (K + 1) / 2;
+        {
+            uint4 x[H];
+#pragma unroll
+            for (int c = 0; c < H; ++c) x[c] = ld16(as_row(lane_value(p, c)) + off);
+            enc_mac16<K, M, 0, H>(s, x, tab);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // the second half's loads stay below the first half's multiply
+        {
+            uint4 x[K - H];
+#pragma unroll
+            for (int c = 0; c < K - H; ++c) x[c] = ld16(as_row(lane_value(p, H + c)) + off);
+            enc_mac16<K, M, H, K - H>(s, x, tab);
+        }
+    } else {
+        uint4 x[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) x[c] = ld16(as_row(lane_value(p, c)) + off);
+        enc_mac16<K, M, 0, K>(s, x, tab);
+    }
+#pragma unroll
+    for (int r = 0; r < M; ++r) xor16(s[r], par[r]);
+}
+
+// lane s < k + m: the address of shard s of group g; the rest zero
+__device__ __forceinline__ uint64_t lane_row(const uint64_t* __restrict__ dptrs, const uint64_t* __restrict__ pptrs,
+                                             uint64_t g, int k, int m, int lane) {
+    uint64_t p = 0;
+    if (lane < k) p = dptrs[g * (uint64_t)k + lane];
+    else if (lane < k + m) p = pptrs[g * (uint64_t)m + (lane - k)];
+    return p;
 }
 
 }  // namespace qfec

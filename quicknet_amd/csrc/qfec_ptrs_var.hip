@@ -45,25 +45,7 @@
 
 namespace qfec {
 
-// ldv_clip of qfec_ptrs_device.hpp for the templated bodies, without a branch per source.  A lane whose column is not whole
-// in this row loads the column of `safe` instead, a row of the group that is whole wherever a lane
-// works (the group's longest data shard, a parity survivor), and drops it: the loads issue together
-// as in the fixed-length body and no byte at or past len is read.  The row's part column was loaded
-// before the lanes parted, by the lane that holds the row's address and length (lane_part), so the
-// part columns of all rows cost the wave one round trip, at the same time as the whole columns; the
-// lane whose column it is takes it from lane s with readlane.
-template <int D>
-__device__ __forceinline__ void ldv_ragged(uint32_t (&v)[D], const uint8_t* row, const uint8_t* safe, uint32_t off,
-                                           uint32_t len, const uint32_t (&part)[D], uint32_t s) {
-    constexpr uint32_t W = 4u * D;
-    const bool whole = off + W <= len;
-    ldv<D>(v, (whole ? row : safe) + off);
-    const bool mine = len % W != 0 && off == len / W * W;
-#pragma unroll
-    for (int d = 0; d < D; ++d) v[d] = mine ? lane_value32(part[d], s) : whole ? v[d] : 0u;
-}
-
-// ldv_ragged for the reconstruct, whose registers the readlanes above raise (RS(16,4): 93 -> 101
+// ldv_ragged (qfec_ptrs_device.hpp) for the reconstruct, whose registers its readlanes raise (RS(16,4): 93 -> 101
 // VGPRs, 5 -> 4 waves per SIMD, and the full path of all-equal lengths pays for it: 1.14 x the
 // fixed-length call against 1.04): the lane whose column the row's part column is fetches it itself,
 // under a wave-uniform test of whether that column lies in this slab.  One round trip per row
@@ -80,31 +62,6 @@ __device__ __forceinline__ void ldv_ragged_own(uint32_t (&v)[D], const uint8_t* 
     if (pn && (pc >> 6) == slab) {
         if (off == pc * W) ldv_part<D>(v, row + off, pn);
     }
-}
-
-// Every lane of a ragged wave calls it before the first lane-dependent branch.  source: the lane
-// holds the address p and the readable length len of a row the wave reads.  A lane whose row's part
-// column lies in this slab loads it: bytes [len / W * W, len) of the row, zero after them.
-template <int D>
-__device__ __forceinline__ void lane_part(uint32_t (&part)[D], bool source, uint64_t p, uint32_t len, uint32_t slab) {
-    constexpr uint32_t W = 4u * D;
-#pragma unroll
-    for (int d = 0; d < D; ++d) part[d] = 0;
-    const uint32_t pc = len / W, pn = len % W;
-    if (source && pn && (pc >> 6) == slab) ldv_part<D>(part, as_row(p) + pc * W, pn);
-}
-
-__device__ __forceinline__ uint4 ld16_clip(const uint8_t* row, uint32_t off, uint32_t len) {
-    uint32_t v[4];
-    ldv_clip<4>(v, row, off, len);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-__device__ __forceinline__ uint4 ld16_ragged(const uint8_t* row, const uint8_t* safe, uint32_t off, uint32_t len,
-                                             const uint32_t (&part)[4], uint32_t s) {
-    uint32_t v[4];
-    ldv_ragged<4>(v, row, safe, off, len, part, s);
-    return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
 // ------------------------------------------------------------------ encode
@@ -139,19 +96,6 @@ __device__ __forceinline__ void encode_byte_var(int k, int m, const uint32_t* ta
         }
         *out = (uint8_t)acc;
     }
-}
-
-// Sources per pass of the ragged column bodies: the largest divisor of K up to CAP.  The ragged bodies
-// are loops rolled over the sources in such chunks, not the unrolled bodies of the fixed-length
-// kernels: a kernel's registers are those of its larger path, and unrolled next to the full path the
-// ragged encode of RS(16,4) holds 238 VGPRs (2 waves per SIMD) and the ragged reconstruct 101 (4 waves),
-// where the full paths alone hold 93 and 94.
-template <int K, int CAP>
-constexpr int ragged_chunk() {
-    int best = 1;
-    for (int d = 2; d <= CAP && d <= K; ++d)
-        if (K % d == 0) best = d;
-    return best;
 }
 
 // encode_column on a ragged wave: row(c), len(c) = address and length of data shard c (c wave-uniform,

@@ -20,6 +20,8 @@
 //                      shards given as a device table of addresses)
 //   qfec_integrity_ptrs.cpp  qfec_verify_ptrs, qfec_locate_ptrs, qfec_scrub_ptrs (the parity check and single-shard
 //                      error location on shards given as a device table of addresses)
+//   qfec_integrity_ptrs_var.cpp  qfec_verify_ptrs_var, qfec_locate_ptrs_var, qfec_scrub_ptrs_var (the same where every
+//                      data shard has its own length; the scrub corrects from one parity row, without a plan)
 //   qfec_check.cpp     qfec_check_build / qfec_check_apply, qfec_locate_wide / qfec_scrub_wide (check plans built
 //                      on the device: single-shard error location at any k + m), qfec_check_build_host
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
@@ -327,6 +329,12 @@ int run_locate(DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_
 // table's own order
 int run_locate_ptrs(DevCtx& ctx, qfec_code* code, const uint64_t* dptrs, const uint64_t* pptrs, long long groups,
                     int block_size, int* d_culprit, uint8_t* d_marks, unsigned* d_counts, hipStream_t s);
+// the same where every data shard has its own length (qfec_integrity_ptrs_var.cpp): lens [groups * k] in table
+// order, glen [groups] the length of each group's parity shards; a group refused for its lengths gets
+// QFEC_LOC_INVALID and is counted into d_invalid (nullable)
+int run_locate_ptrs_var(DevCtx& ctx, qfec_code* code, const uint64_t* dptrs, const uint64_t* pptrs, const int32_t* lens,
+                        const int32_t* glen, long long groups, int max_len, int* d_culprit, uint8_t* d_marks,
+                        unsigned* d_counts, unsigned* d_invalid, hipStream_t s);
 // locate(marks, extra), then qfec_repair with the marks it wrote; both from stream-ordered scratch
 // (`extra` bytes follow the marks)
 int run_scrub(const char* who, qfec_code* code, uint8_t* d_data, uint8_t* d_parity, long long groups, int block_size,
