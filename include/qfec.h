@@ -478,6 +478,95 @@ int qfec_update(qfec_code *code,
                 long long groups, int block_size, long long pitch,
                 unsigned int *d_invalid       /* counter, accumulates, nullable */, void *stream);
 
+/* Incremental parity on shards scattered in device memory: qfec_encode_update and qfec_update on the
+ * table of qfec_encode_ptrs (groups * k data addresses, group-major, then groups * m parity addresses),
+ * each with and without a length per shard.  For a sender whose packets arrive one at a time, ragged,
+ * in their own buffers, and for a store that replaces one packet where it lies.  Common to all four:
+ *   Arithmetic: true GF(2^8) products from the code's parity rows, as in qfec_encode_update; the rs.c
+ *     stale-row quirk is never applied.  Any code qfec_code_new accepts: there is no k + m limit.
+ *   Asynchronous on `stream`: no host synchronisation, no LUT, no scratch, no read-back.  A batch
+ *     beyond one launch's index space goes in several launches.
+ *   No byte outside a shard's stated extent is read or written on any path.
+ *   A table entry a call does not address is never dereferenced, takes no part in the alignment
+ *     judgement and may hold anything, so a sender can fill the table as packets arrive.
+ *   Alignment, judged per group on the device on the entries the group may dereference: all of them
+ *     16-B aligned, the group runs 16-byte lanes over its whole columns and the tail bytes byte by
+ *     byte; any other group is worked on byte by byte, much slower.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in qfec_last_error
+ *     after the call's name: a null code, first < 0, count < 1, first + count > k, groups < 0,
+ *     block_size < 1 or max_len < 1, accumulate or delta_only not 0 or 1, and with groups > 0 a null
+ *     d_shards, d_shard, d_new, d_lens, d_group_len or d_new_len where the call takes it (d_lens may be
+ *     NULL in delta mode; d_invalid may always be NULL).  groups == 0 or m == 0 returns QFEC_OK and
+ *     launches nothing; a bad argument still wins over that.
+ *
+ * qfec_encode_update_ptrs, the range form: for every group and parity row j
+ *   parity_j[0, block_size) (^)= sum_{c < count} rows[j][first + c] x data_{first + c}[0, block_size)
+ * It dereferences only the data entries first .. first + count - 1 and the m parity entries of a group.
+ * accumulate = 1 XORs into the parity, 0 overwrites it.  Over any partition of [0, k), the first piece
+ * overwriting and the others accumulating, bytes [0, block_size) of the parity are what
+ * qfec_encode_ptrs writes, for codes without a quirk-stale coefficient.
+ *
+ * qfec_update_ptrs, the per-group form: d_new is a DEVICE array of `groups` addresses of block_size
+ * bytes each, and i = d_shard[g] names the ONE data shard group g replaces.
+ *   i < 0        nothing of the group is read or written: not d_new[g], not one of its table entries.
+ *   i >= k       the group is untouched and counted once into *d_invalid (accumulated, not reset).  No
+ *                table is indexed with such an id.
+ *   otherwise    delta_only = 0: with delta = shard i ^ new, every parity shard has rows[j][i] x delta
+ *                XORed in and shard i becomes new.  delta_only = 1: d_new[g] is the delta itself, no
+ *                data entry is dereferenced and only the parity is written.
+ * d_new[g] must not overlap a shard the call writes.
+ *
+ * qfec_encode_update_ptrs_var: the range form where part c of group g has d_lens[g*k + first + c] bytes
+ * (d_lens holds groups * k ints; only the entries of the range are read) and L = d_group_len[g] is an
+ * INPUT: the extent of the group's parity shards that the caller keeps, for example the MTU.
+ *   Invalid group: L outside [0, max_len], or a length of the range outside [0, L] (INT_MIN and
+ *     INT_MAX included).  It is untouched and counted once into *d_invalid.  A length outside the
+ *     range is not looked at.  L = 0: nothing is dereferenced.
+ *   A part is read in [0, len) only and counts as zero from there; a part of length 0 is never
+ *     dereferenced.
+ *   accumulate = 0: exactly [0, L) of every parity shard is written, zero past the longest part.
+ *   accumulate = 1, e the longest part of the range: [0, e) is read and rewritten, [e, L) is neither
+ *     read nor written.  Nothing at or past L is touched either way.
+ *   Over any partition of [0, k), the first piece overwriting: [0, max_i len_i) is what
+ *     qfec_encode_ptrs_var writes (codes without a quirk-stale coefficient), [max_i len_i, L) is zero,
+ *     and qfec_verify_ptrs_var with this L reports 0.
+ *
+ * qfec_update_ptrs_var: the per-group form with i = d_shard[g], L = d_group_len[g], n = d_new_len[g]
+ * the length of the new row and o = d_lens[g*k + i] the length shard i has now.  In delta mode o and
+ * the data entry are not read (d_lens may be NULL) and e = n; else e = max(o, n).
+ *   i < 0 and i >= k as for qfec_update_ptrs.  Invalid group, counted once: L outside [0, max_len], or
+ *     n or o outside [0, L].  No other length of the group is read.
+ *   Old is read in [0, o) and new in [0, n); both count as zero beyond.  [0, e) of every parity shard
+ *     is read, XORed and rewritten; nothing at or past e is touched.  Exactly [0, n) of shard i is
+ *     written: the shard must have room for n bytes, and its bytes [n, o) keep their old values -- they
+ *     are past the new length.  n = 0: d_new[g] is never dereferenced; n = 0 and o = 0: a valid no-op.
+ *   d_lens is const: other waves of the group read it during the launch.  THE CALLER stores n at
+ *     d_lens[g*k + i] afterwards, stream-ordered, before the lengths are used again.
+ *   If the parity equalled the encode of the zero-padded old data over [0, L), it now equals the
+ *     encode of the zero-padded new data over [0, L). */
+int qfec_encode_update_ptrs(qfec_code *code, int first, int count,
+                            unsigned char *const *d_shards /* groups * (k + m) device addresses */,
+                            long long groups, int block_size,
+                            int accumulate /* 1: XOR into the parity, 0: overwrite it */, void *stream);
+int qfec_update_ptrs(qfec_code *code, unsigned char *const *d_shards,
+                     const int *d_shard                  /* [groups]: 0..k-1 replaced; < 0 = group untouched */,
+                     const unsigned char *const *d_new   /* [groups] device addresses: the new rows (or the deltas) */,
+                     int delta_only, long long groups, int block_size,
+                     unsigned int *d_invalid             /* counter, accumulates, nullable */, void *stream);
+int qfec_encode_update_ptrs_var(qfec_code *code, int first, int count, unsigned char *const *d_shards,
+                                const int *d_lens       /* [groups * k] */,
+                                const int *d_group_len  /* [groups], read */,
+                                long long groups, int max_len, int accumulate,
+                                unsigned int *d_invalid /* counter, accumulates, nullable */, void *stream);
+int qfec_update_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                         const int *d_lens       /* [groups * k]; NULL allowed with delta_only = 1 */,
+                         const int *d_group_len  /* [groups] */,
+                         const int *d_shard      /* [groups] */,
+                         const unsigned char *const *d_new /* [groups] device addresses */,
+                         const int *d_new_len    /* [groups] */,
+                         int delta_only, long long groups, int max_len,
+                         unsigned int *d_invalid /* counter, accumulates, nullable */, void *stream);
+
 /* Which shard is wrong?  qfec_verify says whether a group's parity matches its data; qfec_locate
  * names the ONE shard, data or parity, whose corruption explains the mismatch, so that it can be
  * marked for qfec_repair.  A code with m >= 2 parity rows has minimum distance m + 1 >= 3 and can

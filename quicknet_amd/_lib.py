@@ -20,6 +20,7 @@ EXPORTS = {
                "qfec_repair", "qfec_prepare_repair", "qfec_repair_rows", "qfec_verify",
                "qfec_encode_update", "qfec_update", "qfec_encode_ptrs", "qfec_reconstruct_ptrs",
                "qfec_encode_ptrs_var", "qfec_reconstruct_ptrs_var",
+               "qfec_encode_update_ptrs", "qfec_update_ptrs", "qfec_encode_update_ptrs_var", "qfec_update_ptrs_var",
                "qfec_plan_stride", "qfec_plan_build", "qfec_plan_apply", "qfec_reconstruct_wide", "qfec_repair_wide",
                "qfec_plan_build_host", "qfec_plan_apply_ptrs", "qfec_reconstruct_ptrs_wide", "qfec_repair_ptrs_wide",
                "qfec_plan_apply_ptrs_var", "qfec_reconstruct_ptrs_wide_var", "qfec_repair_ptrs_wide_var",
@@ -95,6 +96,10 @@ def lib():
         "qfec_verify": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_encode_update": (i, [vp, i, i, vp, vp, ll, i, ll, i, vp]),
         "qfec_update": (i, [vp, vp, vp, vp, vp, ll, i, ll, vp, vp]),
+        "qfec_encode_update_ptrs": (i, [vp, i, i, vp, ll, i, i, vp]),
+        "qfec_update_ptrs": (i, [vp, vp, vp, vp, i, ll, i, vp, vp]),
+        "qfec_encode_update_ptrs_var": (i, [vp, i, i, vp, vp, vp, ll, i, i, vp, vp]),
+        "qfec_update_ptrs_var": (i, [vp, vp, vp, vp, vp, vp, vp, i, ll, i, vp, vp]),
         "qfec_encode_ptrs": (i, [vp, vp, ll, i, vp]),
         "qfec_reconstruct_ptrs": (i, [vp, vp, vp, ll, i, vp, vp]),
         "qfec_encode_ptrs_var": (i, [vp, vp, vp, ll, i, vp, vp, vp]),

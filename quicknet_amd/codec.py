@@ -338,6 +338,79 @@ class Code:
                                               _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
               "qfec_reconstruct_ptrs_var")
 
+    def _range_args(self, what, first, count):
+        first, count = int(first), int(count)
+        if first < 0 or count < 1 or first + count > self.k:
+            raise QfecError(f"{what}: data shards [{first}, {first + count}) are not inside [0, {self.k})")
+        return first, count
+
+    def _per_group_args(self, what, G, shard, new):
+        import torch
+        self._int32_count(what, "shard", shard, G)
+        if new.dtype != torch.int64 or new.numel() != G:
+            raise QfecError(f"{what}: new has dtype {new.dtype} and {new.numel()} elements, {G} int64 addresses expected")
+
+    def encode_update_ptrs(self, ptrs, first, count, block_size, accumulate=True, stream=None):
+        """encode_update() on shards scattered in device memory (qfec_encode_update_ptrs): parity_j (^)=
+        sum_c rows[j][first + c] x data shard first + c, over [0, block_size).  ptrs as for encode_ptrs;
+        only the data entries first .. first + count - 1 and the parity entries of a group are
+        dereferenced, the others may hold anything.  accumulate: XOR into the parity (True) or
+        overwrite it (False).  True GF products, no rs.c stale-row quirk."""
+        G = self._ptr_groups("encode_update_ptrs", ptrs)
+        first, count = self._range_args("encode_update_ptrs", first, count)
+        check(lib().qfec_encode_update_ptrs(self._h, first, count, _dev_ptr(ptrs, _I64, "ptrs"), G, int(block_size),
+                                            int(bool(accumulate)), _stream_handle(stream)), "qfec_encode_update_ptrs")
+
+    def update_ptrs(self, ptrs, shard, new, block_size, delta_only=False, invalid=None, stream=None):
+        """update() on shards scattered in device memory (qfec_update_ptrs).  ptrs as for encode_ptrs;
+        shard: device int32 [G] as for update(); new: device int64 [G], the address of every group's new
+        row of block_size bytes -- or, with delta_only, of its delta old ^ new: then no data entry is
+        dereferenced and only the parity is written.  Nothing of a group with a negative id is read,
+        its entry of `new` included.  invalid: optional device int32/uint32 [1] counter of groups with
+        an id >= k (accumulates)."""
+        G = self._ptr_groups("update_ptrs", ptrs)
+        self._per_group_args("update_ptrs", G, shard, new)
+        check(lib().qfec_update_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(shard, _I32, "shard"),
+                                     _dev_ptr(new, _I64, "new"), int(bool(delta_only)), G, int(block_size),
+                                     _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)), "qfec_update_ptrs")
+
+    def encode_update_ptrs_var(self, ptrs, first, count, lens, group_len, max_len, accumulate=True, invalid=None,
+                               stream=None):
+        """encode_update_ptrs() on shards that each have their own length (qfec_encode_update_ptrs_var).
+        lens: int32 [G*k] on device (only the entries of the range are read); group_len: int32 [G] on
+        device, an INPUT: the extent L of every group's parity shards.  Overwriting writes exactly [0, L),
+        zero past the longest part; accumulating rewrites [0, longest part of the range) only.  invalid:
+        optional device int32/uint32 [1] counter of groups refused for their lengths (accumulates)."""
+        G = self._ptr_groups("encode_update_ptrs_var", ptrs)
+        first, count = self._range_args("encode_update_ptrs_var", first, count)
+        self._int32_count("encode_update_ptrs_var", "lens", lens, G * self.k)
+        self._int32_count("encode_update_ptrs_var", "group_len", group_len, G)
+        check(lib().qfec_encode_update_ptrs_var(self._h, first, count, _dev_ptr(ptrs, _I64, "ptrs"),
+                                                _dev_ptr(lens, _I32, "lens"), _dev_ptr(group_len, _I32, "group_len"), G,
+                                                int(max_len), int(bool(accumulate)), _dev_ptr(invalid, _I32, "invalid"),
+                                                _stream_handle(stream)), "qfec_encode_update_ptrs_var")
+
+    def update_ptrs_var(self, ptrs, lens, group_len, shard, new, new_len, max_len, delta_only=False, invalid=None,
+                        stream=None):
+        """update_ptrs() on shards that each have their own length (qfec_update_ptrs_var).  lens: int32
+        [G*k] on device, read at the replaced shard only (None allowed with delta_only); group_len: int32
+        [G]; new_len: int32 [G], the length of every new row.  Exactly [0, new_len) of the replaced shard
+        and [0, max(old, new length)) of the parity shards are rewritten.  lens is NOT written: store
+        new_len at lens[g*k + shard[g]] afterwards, on the same stream."""
+        G = self._ptr_groups("update_ptrs_var", ptrs)
+        self._per_group_args("update_ptrs_var", G, shard, new)
+        if lens is not None or not delta_only:
+            if lens is None:
+                raise QfecError("update_ptrs_var: lens may be None with delta_only alone")
+            self._int32_count("update_ptrs_var", "lens", lens, G * self.k)
+        self._int32_count("update_ptrs_var", "group_len", group_len, G)
+        self._int32_count("update_ptrs_var", "new_len", new_len, G)
+        check(lib().qfec_update_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                         _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(shard, _I32, "shard"),
+                                         _dev_ptr(new, _I64, "new"), _dev_ptr(new_len, _I32, "new_len"),
+                                         int(bool(delta_only)), G, int(max_len), _dev_ptr(invalid, _I32, "invalid"),
+                                         _stream_handle(stream)), "qfec_update_ptrs_var")
+
     def prepare_repair(self):
         check(lib().qfec_prepare_repair(self._h), "qfec_prepare_repair")
 

@@ -182,6 +182,29 @@ struct PtrsVarArgs {
     unsigned int* invalid;       // counter of groups refused for their lengths; may be NULL
 };
 
+// incremental parity on a table of shard addresses (qfec_update_ptrs.hip), both forms, with and without
+// per-shard lengths: PtrsArgs' mapping on 16-B lanes with the geometry of `block`, which with lengths
+// is max_len and only sizes the launch (every group cuts its own extent inside the kernel)
+struct UpdatePtrsArgs {
+    const uint64_t* dptrs;       // [groups][k] addresses of the data shards of this launch's groups
+    const uint64_t* pptrs;       // [groups][m] addresses of their parity shards
+    const uint32_t* tab;         // [m][k][QFEC_TAB_STRIDE] (the encode's tables; the stale flag is not used)
+    const int32_t* lens;         // with lengths: [groups][k]; NULL allowed in delta mode of the per-group form
+    const int32_t* group_len;    // with lengths: [groups] the extent of the group's parity shards
+    const int32_t* shard;        // per-group form: [groups] 0..k-1 replaced, < 0 untouched, >= k invalid
+    const uint64_t* news;        // per-group form: [groups] addresses of the new rows (or the deltas)
+    const int32_t* new_len;      // per-group form with lengths: [groups]
+    unsigned int* invalid;       // counter of groups refused for an id or a length; may be NULL
+    uint64_t groups;
+    uint32_t block;              // block_size, or max_len
+    uint32_t vcols, wpg;         // whole 16-B columns per shard; waves per group (PtrsGeom at 16-B lanes)
+    uint32_t tail0, tailn;       // the bytes past the last whole column: first byte, count (< 16)
+    int k, m;
+    int first, count;            // range form: 0 <= first, 1 <= count, first + count <= k
+    int accumulate;              // range form: 1 XOR into the parity, 0 overwrite it
+    int delta_only;              // per-group form: 1 the new rows are deltas and no data entry is dereferenced
+};
+
 // parity check and single-shard error location on a table of shard addresses
 // (qfec_integrity_ptrs.hip): PtrsArgs' mapping on 16-B lanes, the group words of VerifyArgs / LocateArgs
 struct IntegrityPtrsArgs {
@@ -520,6 +543,9 @@ hipError_t launch_encode_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs(const PtrsArgs& a, hipStream_t stream);
 hipError_t launch_encode_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_reconstruct_ptrs_var(const PtrsVarArgs& a, hipStream_t stream);
+// with_lens: the kernels with per-shard lengths (a.group_len, a.lens, a.new_len are read)
+hipError_t launch_encode_update_ptrs(const UpdatePtrsArgs& a, bool with_lens, hipStream_t stream);
+hipError_t launch_update_ptrs(const UpdatePtrsArgs& a, bool with_lens, hipStream_t stream);
 hipError_t launch_verify_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
 hipError_t launch_locate_ptrs(const IntegrityPtrsArgs& a, hipStream_t stream);
 hipError_t launch_verify_ptrs_var(const IntegrityPtrsVarArgs& a, hipStream_t stream);
