@@ -950,6 +950,59 @@ int qfec_scrub_wide(qfec_code *code, unsigned char *d_data, unsigned char *d_par
 int qfec_check_build_host(const qfec_code *code, const unsigned char *marks_n,
                           unsigned char *out_check /* stride bytes */);
 
+/* The check plans on a table of shard addresses: single-shard error location for ANY k + m, beside lost
+ * shards or not, on shards scattered in device memory.  qfec_locate_ptrs takes k <= 32, m <= 32 and
+ * complete groups; these calls are qfec_check_apply / qfec_locate_wide / qfec_scrub_wide, above, on the
+ * table, marks and shards of qfec_reconstruct_ptrs_wide.  A check plan never refers to a layout, so
+ * qfec_check_build and qfec_check_build_host serve a table unchanged.
+ *   Table, marks, shards: d_shards holds groups * (k + m) device addresses in rs.c order -- every
+ *     group's data shards, group-major, then every group's parity shards; d_marks and d_marks_out are
+ *     in the rs.c layout, in the table's own order, so d_marks_out can be handed unchanged to
+ *     qfec_repair_ptrs_wide.  Every shard is exactly block_size bytes at any alignment (no pitch), and
+ *     no byte outside [0, block_size) of any shard is read.  qfec_check_apply_ptrs and
+ *     qfec_locate_ptrs_wide write nothing into any shard, so there shards may alias or repeat.
+ *   Verdicts, counters, codes: d_culprit, d_marks_out and d_counts ([5], accumulated) are what
+ *     qfec_check_apply / qfec_locate_wide / qfec_scrub_wide give for the same rows laid out contiguously;
+ *     the accepted codes are theirs (QFEC_EUNSUP for anything else, m < 2 included, judged on the host
+ *     before a device is touched, also with zero groups and null buffers; narrow codes are accepted).
+ *     d_check follows the same 16-byte rule, and one check plan serves any number of tables while the
+ *     same shards stay lost.
+ *   Marked shards are never dereferenced by qfec_check_apply_ptrs and qfec_locate_ptrs_wide: the plan
+ *     lists the k survivors and the S spares and only those shards are loaded, so the table entries of
+ *     marked shards may hold anything; groups whose plan has status 0 or 2 read nothing.  In
+ *     qfec_scrub_ptrs_wide the entries of marked shards must be real buffers of block_size bytes, for
+ *     the repair writes them; a written shard must not overlap any other shard of the batch
+ *     (qfec_repair_ptrs_wide's rule), or the result is undefined.
+ *   Alignment is judged per group on the device, from the entries of the group's unmarked shards only:
+ *     a group whose unmarked shards all start on a 16-byte boundary runs 16-byte lanes over its whole
+ *     columns and its block_size % 16 tail bytes byte by byte; any other group runs byte by byte, much
+ *     slower.
+ *   qfec_locate_ptrs_wide is qfec_check_build into stream-ordered scratch followed by
+ *     qfec_check_apply_ptrs, the batch cut so that one chunk's plans stay under 64 MiB; d_marks may be
+ *     NULL (complete groups) and d_marks_out may be d_marks itself.
+ *   qfec_scrub_ptrs_wide is that locate into stream-ordered scratch marks followed by
+ *     qfec_repair_ptrs_wide with them, under qfec_scrub_wide's rules: a located culprit and the lost shards
+ *     of its group are rewritten to the original bytes; MULTI and AMBIGUOUS groups get no marks and are
+ *     untouched byte for byte; LOST groups are untouched and counted into *d_failed (may be NULL);
+ *     UNCHECKED groups, and CLEAN groups with losses, are repaired as qfec_repair_ptrs_wide repairs them.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in qfec_last_error
+ *     after the call's name: a null code, groups < 0, block_size < 1, and with groups > 0 a null
+ *     d_shards, a null d_check, for qfec_check_apply_ptrs and qfec_locate_ptrs_wide a null d_culprit; a
+ *     d_check that is not 16-byte aligned.  groups == 0 returns QFEC_OK and launches nothing. */
+int qfec_check_apply_ptrs(qfec_code *code, unsigned char *const *d_shards, const unsigned char *d_check,
+                          long long groups, int block_size, int *d_culprit /* [groups] */,
+                          unsigned char *d_marks_out /* rs.c layout, nullable */,
+                          unsigned int *d_counts /* [5], nullable */, void *stream);
+int qfec_locate_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
+                          const unsigned char *d_marks /* nullable: complete groups */, long long groups,
+                          int block_size, int *d_culprit /* [groups] */,
+                          unsigned char *d_marks_out /* nullable, may equal d_marks */,
+                          unsigned int *d_counts /* [5], nullable */, void *stream);
+int qfec_scrub_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
+                         const unsigned char *d_marks /* nullable */, long long groups, int block_size,
+                         int *d_culprit /* nullable */, unsigned int *d_counts /* [5], nullable */,
+                         unsigned int *d_failed /* qfec_repair_ptrs_wide's counter, nullable */, void *stream);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

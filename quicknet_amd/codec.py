@@ -629,9 +629,10 @@ class Code:
         every marked shard has room for group_len bytes."""
         self._ptrs_wide_var("qfec_repair_ptrs_wide_var", ptrs, lens, group_len, marks, max_len, failed, invalid, stream)
 
-    def _ptrs_out(self, what, ptrs, out, out_name, counts=None):
-        """The checks verify_ptrs / locate_ptrs / scrub_ptrs share -> (G, out): out is the call's
-        per-group device int32 [G] result, allocated when not given; counts is checked when given."""
+    def _ptrs_out(self, what, ptrs, out, out_name, counts=None, ncounts=3):
+        """The checks verify_ptrs / locate_ptrs / scrub_ptrs and the wide locates on tables share ->
+        (G, out): out is the call's per-group device int32 [G] result, allocated when not given; counts
+        is checked when given."""
         import torch
         G = self._ptr_groups(what, ptrs)
         if out is None:
@@ -641,8 +642,8 @@ class Code:
                 raise QfecError(f"{what}: {out_name} has {out.numel()} elements for {G} groups")
             if out.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
                 raise QfecError(f"{what}: {out_name} has dtype {out.dtype}, a 4-byte integer expected")
-        if counts is not None and counts.numel() != 3:
-            raise QfecError(f"{what}: counts has {counts.numel()} elements, not 3")
+        if counts is not None and counts.numel() != ncounts:
+            raise QfecError(f"{what}: counts has {counts.numel()} elements, not {ncounts}")
         return G, out
 
     def verify_ptrs(self, ptrs, block_size, bad_rows=None, bad_groups=None, stream=None):
@@ -957,6 +958,54 @@ class Code:
                                     _dev_ptr(marks, what="marks"), G, block_size, pitch,
                                     _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(counts, _I32, "counts"),
                                     _dev_ptr(failed, _I32, "failed"), _stream_handle(stream)), "qfec_scrub_wide")
+        return culprit
+
+    def _marks_count(self, what, name, marks, G):
+        if marks is not None and marks.numel() != G * (self.k + self.m):
+            raise QfecError(f"{what}: {name} has {marks.numel()} elements for {G} groups of {self.k + self.m}")
+
+    def check_apply_ptrs(self, ptrs, check_plan, block_size, culprit=None, marks_out=None, counts=None, stream=None):
+        """check_apply() on shards scattered in device memory (qfec_check_apply_ptrs).  ptrs as for
+        encode_ptrs; the entries of shards the plans mark as lost are never dereferenced and nothing is
+        written into a shard; check_plan as for check_apply(); marks_out: optional device uint8
+        [G*k + G*m] in the table's own order, ready for repair_ptrs_wide(); counts: optional device
+        int32/uint32 [5].  Returns culprit."""
+        G, culprit = self._ptrs_out("check_apply_ptrs", ptrs, culprit, "culprit", counts, 5)
+        if check_plan.numel() != G * self.check_stride():
+            raise QfecError(f"check_apply_ptrs: check_plan has {check_plan.numel()} bytes for {G} groups of "
+                            f"{self.check_stride()}")
+        self._marks_count("check_apply_ptrs", "marks_out", marks_out, G)
+        check(lib().qfec_check_apply_ptrs(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(check_plan, what="check_plan"),
+                                          G, int(block_size), _dev_ptr(culprit, _I32, "culprit"),
+                                          _dev_ptr(marks_out, what="marks_out"), _dev_ptr(counts, _I32, "counts"),
+                                          _stream_handle(stream)), "qfec_check_apply_ptrs")
+        return culprit
+
+    def locate_ptrs_wide(self, ptrs, block_size, marks=None, culprit=None, marks_out=None, counts=None, stream=None):
+        """locate_wide() on shards scattered in device memory (qfec_locate_ptrs_wide), at any k + m,
+        beside lost shards or not.  ptrs as for encode_ptrs; marks: uint8 [G*k + G*m] (rs.c layout, the
+        table's own order) or None (complete groups); the entries of marked shards are never
+        dereferenced and nothing is written into a shard.  The other arguments and the result as for
+        locate_wide(); marks_out may be marks itself."""
+        G, culprit = self._ptrs_out("locate_ptrs_wide", ptrs, culprit, "culprit", counts, 5)
+        self._marks_count("locate_ptrs_wide", "marks", marks, G)
+        self._marks_count("locate_ptrs_wide", "marks_out", marks_out, G)
+        check(lib().qfec_locate_ptrs_wide(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(marks, what="marks"), G,
+                                          int(block_size), _dev_ptr(culprit, _I32, "culprit"),
+                                          _dev_ptr(marks_out, what="marks_out"), _dev_ptr(counts, _I32, "counts"),
+                                          _stream_handle(stream)), "qfec_locate_ptrs_wide")
+        return culprit
+
+    def scrub_ptrs_wide(self, ptrs, block_size, marks=None, culprit=None, counts=None, failed=None, stream=None):
+        """locate_ptrs_wide() + repair_ptrs_wide() in one call (qfec_scrub_ptrs_wide), under scrub_wide()'s
+        rules: the located shard and the marked shards of its group are rewritten where they lie, so
+        their entries must be real buffers.  Returns culprit as locate_wide() does."""
+        G, culprit = self._ptrs_out("scrub_ptrs_wide", ptrs, culprit, "culprit", counts, 5)
+        self._marks_count("scrub_ptrs_wide", "marks", marks, G)
+        check(lib().qfec_scrub_ptrs_wide(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(marks, what="marks"), G,
+                                         int(block_size), _dev_ptr(culprit, _I32, "culprit"),
+                                         _dev_ptr(counts, _I32, "counts"), _dev_ptr(failed, _I32, "failed"),
+                                         _stream_handle(stream)), "qfec_scrub_ptrs_wide")
         return culprit
 
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15

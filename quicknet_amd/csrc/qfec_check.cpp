@@ -1,8 +1,9 @@
 // qfec_check.cpp -- single-shard error location at any k + m of the device API in include/qfec.h:
 // qfec_check_build, qfec_check_apply, the one-shot calls qfec_locate_wide (build into stream-ordered
 // scratch, then apply) and qfec_scrub_wide (locate into scratch marks, then qfec_repair_wide), and
-// the host query qfec_check_build_host.  The check plan of a group is computed from its marks on the
-// device (qfec_check.hip) by the arithmetic of qfec_plan.hpp: no LUT, no record per mask, no
+// the host query qfec_check_build_host; and the same on a table of shard addresses: qfec_check_apply_ptrs,
+// qfec_locate_ptrs_wide and qfec_scrub_ptrs_wide (then qfec_repair_ptrs_wide).
+// The check plan of a group is computed from its marks on the device (qfec_check.hip) by the arithmetic of qfec_plan.hpp: no LUT, no record per mask, no
 // read-back and no k + m limit.  Arguments and the code are judged on the host before a device is
 // touched.
 #include "qfec_plan.hpp"
@@ -99,26 +100,19 @@ static CheckGeom check_geom(DevCtx& ctx, const qfec_code* c, const uint8_t* d_da
 }
 
 // the launches over groups [g0, g0 + gn) of a batch of `groups`, whose check plans start at d_check:
-// three presets, the main kernel per chunk, the finish kernel.  d_culprit is the batch's.
-static int run_check_apply(CheckGeom& G, const qfec_code* c, const uint8_t* d_data, const uint8_t* d_par,
-                           const uint8_t* d_check, long long g0, long long gn, long long groups, int* d_culprit,
-                           uint8_t* d_marks_out, unsigned* d_counts, int scrub, hipStream_t s) {
+// three presets, the main kernel per chunk of `per` groups -- launch(c0, cn, flags, cmin, cmax), the
+// words being those of group g0 -- and the finish kernel.  d_culprit is the batch's.
+template <class Launch>
+static int run_check_words(const qfec_code* c, uint32_t stride, long long per, const uint8_t* d_check, long long g0,
+                           long long gn, long long groups, int* d_culprit, uint8_t* d_marks_out, unsigned* d_counts,
+                           int scrub, hipStream_t s, Launch&& launch) {
     GroupWords words(s);  // [gn] flags, lowest candidate, highest candidate
     int rc = words.init("check_apply", gn, 3);
     if (rc) return rc;
     if (hipMemsetAsync(words.at(2), 0, (size_t)gn * 4, s) != hipSuccess)
         return hip_fail(hipGetLastError(), "check_apply: presetting the group words");
-    CheckApplyArgs& a = G.a;
-    rc = for_group_chunks(gn, G.per, [&](long long c0, long long cn) {
-        a.data = d_data + (size_t)(g0 + c0) * a.dgs;
-        a.parity = d_par + (size_t)(g0 + c0) * a.pgs;
-        a.check = d_check + (size_t)c0 * a.stride;
-        a.flags = words.at(0) + c0;
-        a.cmin = words.at(1) + c0;
-        a.cmax = words.at(2) + c0;
-        a.groups = (uint64_t)cn;
-        const hipError_t e = launch_check_apply(a, s);
-        return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_apply kernel launch");
+    rc = for_group_chunks(gn, per, [&](long long c0, long long cn) {
+        return launch(c0, cn, words.at(0) + c0, words.at(1) + c0, words.at(2) + c0);
     });
     if (rc) return rc;
     CheckFinishArgs f{};
@@ -132,7 +126,7 @@ static int run_check_apply(CheckGeom& G, const qfec_code* c, const uint8_t* d_da
     f.groups = (uint64_t)gn;
     f.g0 = (uint64_t)g0;
     f.all_groups = (uint64_t)groups;
-    f.stride = a.stride;
+    f.stride = stride;
     f.k = c->k;
     f.m = c->m;
     f.scrub = scrub;
@@ -140,22 +134,89 @@ static int run_check_apply(CheckGeom& G, const qfec_code* c, const uint8_t* d_da
     return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_finish kernel launch");
 }
 
-// qfec_locate_wide: per chunk, check plans into stream-ordered scratch, apply, free
-static int run_locate_wide(const char* who, DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_par,
-                           const uint8_t* d_marks, long long groups, int block_size, long long pitch, int* d_culprit,
+static int run_check_apply(CheckGeom& G, const qfec_code* c, const uint8_t* d_data, const uint8_t* d_par,
+                           const uint8_t* d_check, long long g0, long long gn, long long groups, int* d_culprit,
                            uint8_t* d_marks_out, unsigned* d_counts, int scrub, hipStream_t s) {
-    CheckGeom G = check_geom(ctx, code, d_data, d_par, block_size, pitch);
-    const long long per = std::max(1ll, std::min(kMaxLaunchLanes / 64, kCheckScratchCap / G.a.stride));
+    CheckApplyArgs& a = G.a;
+    return run_check_words(c, a.stride, G.per, d_check, g0, gn, groups, d_culprit, d_marks_out, d_counts, scrub, s,
+                           [&](long long c0, long long cn, unsigned* flags, unsigned* cmin, unsigned* cmax) {
+                               a.data = d_data + (size_t)(g0 + c0) * a.dgs;
+                               a.parity = d_par + (size_t)(g0 + c0) * a.pgs;
+                               a.check = d_check + (size_t)c0 * a.stride;
+                               a.flags = flags;
+                               a.cmin = cmin;
+                               a.cmax = cmax;
+                               a.groups = (uint64_t)cn;
+                               const hipError_t e = launch_check_apply(a, s);
+                               return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_apply kernel launch");
+                           });
+}
+
+// the same on a table of shard addresses: dptrs / pptrs are the two halves of the batch's table
+static int run_check_apply_ptrs(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
+                                const uint8_t* d_check, long long g0, long long gn, long long groups, int block,
+                                int* d_culprit, uint8_t* d_marks_out, unsigned* d_counts, int scrub, hipStream_t s) {
+    CheckPtrsArgs a{};
+    const PtrsGeom p = ptrs_geom(block, 16);
+    a.t256 = ctx.d_t256;
+    a.k = c->k;
+    a.m = c->m;
+    a.block = (uint32_t)block;
+    a.stride = (uint32_t)check_layout(c->k, c->m).stride;
+    a.vcols = p.vcols;
+    a.wpg = p.wpg;
+    a.tail0 = p.tail0;
+    a.tailn = p.tailn;
+    return run_check_words(c, a.stride, p.per, d_check, g0, gn, groups, d_culprit, d_marks_out, d_counts, scrub, s,
+                           [&](long long c0, long long cn, unsigned* flags, unsigned* cmin, unsigned* cmax) {
+                               a.dptrs = dptrs + (size_t)(g0 + c0) * a.k;
+                               a.pptrs = pptrs + (size_t)(g0 + c0) * a.m;
+                               a.check = d_check + (size_t)c0 * a.stride;
+                               a.flags = flags;
+                               a.cmin = cmin;
+                               a.cmax = cmax;
+                               a.groups = (uint64_t)cn;
+                               const hipError_t e = launch_check_apply_ptrs(a, s);
+                               return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_apply_ptrs kernel launch");
+                           });
+}
+
+// the one-shot locates: per chunk, check plans into stream-ordered scratch, apply(g0, gn, plans), free
+template <class Apply>
+static int locate_wide_chunks(const char* who, DevCtx& ctx, qfec_code* code, const uint8_t* d_marks, long long groups,
+                              hipStream_t s, Apply&& apply) {
+    const long long stride = check_layout(code->k, code->m).stride;
+    const long long per = std::max(1ll, std::min(kMaxLaunchLanes / 64, kCheckScratchCap / stride));
     return for_group_chunks(groups, per, [&](long long g0, long long gn) {
         uint8_t* chk = nullptr;
-        if (hipMallocAsync((void**)&chk, (size_t)gn * G.a.stride, s) != hipSuccess)
+        if (hipMallocAsync((void**)&chk, (size_t)gn * stride, s) != hipSuccess)
             return hip_fail(hipGetLastError(), (std::string(who) + " scratch").c_str());
         // rs.c layout: every group's data marks, then the parity marks
         int r = run_check_build(ctx, code, d_marks ? d_marks + (size_t)g0 * code->k : nullptr,
                                 d_marks ? d_marks + (size_t)groups * code->k + (size_t)g0 * code->m : nullptr, gn, chk, s);
-        if (!r) r = run_check_apply(G, code, d_data, d_par, chk, g0, gn, groups, d_culprit, d_marks_out, d_counts, scrub, s);
+        if (!r) r = apply(g0, gn, chk);
         (void)hipFreeAsync(chk, s);
         return r;
+    });
+}
+
+// qfec_locate_wide
+static int run_locate_wide(const char* who, DevCtx& ctx, qfec_code* code, const uint8_t* d_data, const uint8_t* d_par,
+                           const uint8_t* d_marks, long long groups, int block_size, long long pitch, int* d_culprit,
+                           uint8_t* d_marks_out, unsigned* d_counts, int scrub, hipStream_t s) {
+    CheckGeom G = check_geom(ctx, code, d_data, d_par, block_size, pitch);
+    return locate_wide_chunks(who, ctx, code, d_marks, groups, s, [&](long long g0, long long gn, const uint8_t* chk) {
+        return run_check_apply(G, code, d_data, d_par, chk, g0, gn, groups, d_culprit, d_marks_out, d_counts, scrub, s);
+    });
+}
+
+// qfec_locate_ptrs_wide: t is the table, data entries first
+static int run_locate_ptrs_wide(const char* who, DevCtx& ctx, qfec_code* code, const uint64_t* t, const uint8_t* d_marks,
+                                long long groups, int block_size, int* d_culprit, uint8_t* d_marks_out,
+                                unsigned* d_counts, int scrub, hipStream_t s) {
+    return locate_wide_chunks(who, ctx, code, d_marks, groups, s, [&](long long g0, long long gn, const uint8_t* chk) {
+        return run_check_apply_ptrs(ctx, code, t, t + (size_t)groups * code->k, chk, g0, gn, groups, block_size, d_culprit,
+                                    d_marks_out, d_counts, scrub, s);
     });
 }
 
@@ -253,6 +314,55 @@ int qfec_scrub_wide(qfec_code* code, unsigned char* d_data, unsigned char* d_par
     rc = run_locate_wide(who, *ctx, code, d_data, d_parity, d_marks, groups, block_size, pitch, d_culprit, marks, d_counts,
                          1, s);
     if (!rc) rc = qfec_repair_wide(code, d_data, d_parity, marks, groups, block_size, pitch, d_failed, stream);
+    (void)hipFreeAsync(marks, s);
+    return rc;
+}
+
+int qfec_check_apply_ptrs(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_check, long long groups,
+                          int block_size, int* d_culprit, unsigned char* d_marks_out, unsigned int* d_counts,
+                          void* stream) {
+    const char* who = "qfec_check_apply_ptrs";
+    const char* why = bad_table_args(code, d_shards, groups, block_size);
+    if (!why && groups > 0) why = !d_check ? "null d_check" : !d_culprit ? "null d_culprit" : nullptr;
+    if (!why && plan_misaligned(d_check)) why = "d_check not 16-byte aligned";
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    const int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    const uint64_t* t = reinterpret_cast<const uint64_t*>(d_shards);
+    return run_check_apply_ptrs(*ctx, code, t, t + (size_t)groups * code->k, d_check, 0, groups, groups, block_size,
+                                d_culprit, d_marks_out, d_counts, 0, (hipStream_t)stream);
+}
+
+int qfec_locate_ptrs_wide(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_marks, long long groups,
+                          int block_size, int* d_culprit, unsigned char* d_marks_out, unsigned int* d_counts,
+                          void* stream) {
+    const char* who = "qfec_locate_ptrs_wide";
+    const char* why = bad_table_args(code, d_shards, groups, block_size);
+    if (!why && groups > 0 && !d_culprit) why = "null d_culprit";
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    const int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    return run_locate_ptrs_wide(who, *ctx, code, reinterpret_cast<const uint64_t*>(d_shards), d_marks, groups, block_size,
+                                d_culprit, d_marks_out, d_counts, 0, (hipStream_t)stream);
+}
+
+int qfec_scrub_ptrs_wide(qfec_code* code, unsigned char* const* d_shards, const unsigned char* d_marks, long long groups,
+                         int block_size, int* d_culprit, unsigned int* d_counts, unsigned int* d_failed, void* stream) {
+    const char* who = "qfec_scrub_ptrs_wide";
+    const char* why = bad_table_args(code, d_shards, groups, block_size);
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* marks = nullptr;  // the locate's marks_out, then the repair's marks
+    if (hipMallocAsync((void**)&marks, (size_t)groups * (size_t)(code->k + code->m), s) != hipSuccess)
+        return hip_fail(hipGetLastError(), "scrub_ptrs_wide scratch");
+    rc = run_locate_ptrs_wide(who, *ctx, code, reinterpret_cast<const uint64_t*>(d_shards), d_marks, groups, block_size,
+                              d_culprit, marks, d_counts, 1, s);
+    if (!rc) rc = qfec_repair_ptrs_wide(code, d_shards, marks, groups, block_size, d_failed, stream);
     (void)hipFreeAsync(marks, s);
     return rc;
 }

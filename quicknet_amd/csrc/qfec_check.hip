@@ -25,9 +25,16 @@
 // unexplained).  One candidate over every wave and pass and no unexplained byte is exactly "this
 // shard's relation holds in every byte, and no other's does".  With one spare only the flag is set.
 // k_check_finish turns the words and the plan's head into verdicts, marks and counts.
+//
+// k_check_apply_ptrs: the same arithmetic and cold path (check_columns) where the rows are given by a
+// device table of shard addresses (qfec_check_apply_ptrs), in the mapping of k_plan_apply_ptrs; the
+// words and the finish kernel are the same.
+#include <type_traits>
+
 #include "../../include/qfec.h"
 #include "qfec_device.hpp"
 #include "qfec_plan.hpp"
+#include "qfec_ptrs_device.hpp"
 
 namespace qfec {
 
@@ -249,6 +256,224 @@ __global__ void __launch_bounds__(256) k_check_apply(CheckApplyArgs a, const uin
     }
 }
 
+// k_check_apply's body for k_check_apply_ptrs: 64 lanes of D dwords each (D = 4: the 16 bytes, D = 1: the
+// byte at `off` of every shard) through the group's check plan `chk`, S spares.  row(s): where shard s
+// starts, s wave-uniform.  A lane that is not `live` has no bytes at `off`: it issues no load and
+// carries zero, which every candidate explains; a live lane's bytes all count, so nothing is masked.
+// The call is wave-uniform (ballots and readlane inside) and folds what it finds into the group's
+// three words.  False: not a check plan of this code, nothing more to do.
+// (The two bodies stay apart: as one function this text moved k_check_apply<4>'s SGPR count.)
+template <int D, class Row>
+__device__ __forceinline__ bool check_columns(const uint8_t* chk, const CheckLayout& CL, cptr32 t256, int k, int n, int S,
+                                              int lane, unsigned int* flags, unsigned int* cmin, unsigned int* cmax,
+                                              const Row& row, uint64_t off, bool live) {
+    static_assert(D == 4 || D == 1, "16-B columns or bytes");
+    const cptr32 pw = (cptr32)chk;
+    auto ld = [&](uint32_t(&v)[D], uint32_t s) {
+        const uint8_t* r = row(s);  // every lane takes part in the readlane
+#pragma unroll
+        for (int d = 0; d < D; ++d) v[d] = 0;
+        if (live) check_ld<D>(v, r + off);
+    };
+    uint32_t s0[D];  // the first spare's syndrome, from pass 0
+#pragma unroll
+    for (int d = 0; d < D; ++d) s0[d] = 0;
+    for (int x0 = 0; x0 < S; x0 += CCH) {
+        uint32_t acc[CCH][D];
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc[j][d] = 0;
+        for (int c = 0; c < k; ++c) {
+            const uint32_t s = check_u8(pw, QFEC_CHECK_IDS + c);
+            if (s >= (uint32_t)n) return false;  // not a check plan of this code
+            uint32_t v[D];
+            ld(v, s);
+            Sel sl[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) sl[d] = gf_sel(v[d]);
+#pragma unroll
+            for (int j = 0; j < CCH; ++j)
+                if (x0 + j < S) {
+                    const cptr32 tc = t256 + check_u8(pw, CL.a_off + (x0 + j) * k + c) * QFEC_TAB_STRIDE;
+                    const uint32_t t0 = tc[0], t1 = tc[1], t2 = tc[2], t3 = tc[3], t4 = tc[4];
+#pragma unroll
+                    for (int d = 0; d < D; ++d)
+                        acc[j][d] = xor3(acc[j][d], pp0(sl[d], t0, t1), pp1(sl[d], t2, t3)) ^ pp2(sl[d], t4);
+                }
+        }
+        uint32_t nz[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) nz[d] = 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (x0 + j < S) {
+                const uint32_t sp = check_u8(pw, QFEC_CHECK_IDS + k + x0 + j);
+                if (sp >= (uint32_t)n) return false;
+                uint32_t p[D];
+                ld(p, sp);
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    acc[j][d] ^= p[d];
+                    nz[d] |= acc[j][d];
+                }
+            }
+        if (x0 == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) s0[d] = acc[0][d];
+        }
+        uint32_t any = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            nz[d] |= s0[d];
+            any |= nz[d];
+        }
+        const uint64_t hot = __ballot(any != 0);
+        if (!hot) continue;  // consistent so far: the common case ends with the loop
+
+        // ---- cold: one candidate from one byte, then every lane's bytes against it
+        if (S == 1) {  // no ratio to test: the finish kernel calls the group AMBIGUOUS
+            if (lane == 0) atomicOr(flags, 1u);
+            continue;
+        }
+        const int src = __builtin_ctzll(hot);
+        int bsel = 0;
+#pragma unroll
+        for (int d = D - 1; d >= 0; --d)
+            if (nz[d]) bsel = d * 4 + (__builtin_ctz(nz[d]) >> 3);
+        const int b = __builtin_amdgcn_readlane(bsel, src);
+        const uint32_t z0 = check_byte_at<D>(s0, b, src);
+        const int jlo = x0 == 0 ? 1 : 0;  // acc[0] of pass 0 is s0 itself
+        int cnt = 0, first = -1;
+        uint32_t z1 = 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (j >= jlo && x0 + j < S) {
+                const uint32_t zj = check_byte_at<D>(acc[j], b, src);
+                if (j == jlo) z1 = zj;
+                if (zj) {
+                    if (!cnt) first = j;
+                    ++cnt;
+                }
+            }
+        enum { NONE = 0, KPOS, SPARE, SPARE0 };
+        int kind = NONE, cpos = 0;
+        if (z0 == 0) {
+            kind = cnt == 1 ? SPARE : NONE;
+        } else if (cnt == 0) {
+            kind = SPARE0;
+        } else {
+            // the position c of K with ratio[c][x1] . z0 = z1: each lane multiplies its ratio by the
+            // wave-uniform z0 through z0's perm table
+            const cptr32 tz = t256 + z0 * QFEC_TAB_STRIDE;
+            const uint32_t t0 = tz[0], t1 = tz[1], t2 = tz[2], t3 = tz[3], t4 = tz[4];
+            const int x1 = x0 + jlo;
+            for (int c0 = 0; c0 < k; c0 += 64) {
+                const int c = c0 + lane;
+                bool hit = false;
+                if (c < k) {
+                    const uint32_t r = chk[CL.r_off + c * (S - 1) + (x1 - 1)];
+                    hit = (gf_mul4(gf_sel(r), t0, t1, t2, t3, t4) & 0xFFu) == z1;
+                }
+                const uint64_t hits = __ballot(hit);
+                if (hits) {
+                    kind = KPOS;
+                    cpos = c0 + __builtin_ctzll(hits);
+                    break;
+                }
+            }
+        }
+        bool ok = kind != NONE;
+        if (kind == SPARE)
+#pragma unroll
+            for (int d = 0; d < D; ++d) ok = ok && s0[d] == 0;
+#pragma unroll
+        for (int j = 0; j < CCH; ++j)
+            if (j >= jlo && x0 + j < S) {
+                if (kind == KPOS) {
+                    const cptr32 tc = t256 + check_u8(pw, CL.r_off + cpos * (S - 1) + (x0 + j - 1)) * QFEC_TAB_STRIDE;
+                    const uint32_t t0 = tc[0], t1 = tc[1], t2 = tc[2], t3 = tc[3], t4 = tc[4];
+#pragma unroll
+                    for (int d = 0; d < D; ++d) ok = ok && gf_mul4(gf_sel(s0[d]), t0, t1, t2, t3, t4) == acc[j][d];
+                } else if (kind == SPARE0 || j != first) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) ok = ok && acc[j][d] == 0;
+                }
+            }
+        const bool all_ok = kind != NONE && __ballot(!ok) == 0;
+        if (lane == 0) {
+            atomicOr(flags, all_ok ? 1u : 3u);
+            if (all_ok) {
+                const uint32_t id = kind == KPOS    ? check_u8(pw, QFEC_CHECK_IDS + cpos)
+                                    : kind == SPARE ? check_u8(pw, QFEC_CHECK_IDS + k + x0 + first)
+                                                    : check_u8(pw, QFEC_CHECK_IDS + k);
+                atomicMin(cmin, id);
+                atomicMax(cmax, id);
+            }
+        }
+    }
+    return true;
+}
+
+// The same on a table of shard addresses (qfec_check_apply_ptrs): k_plan_apply_ptrs's mapping and
+// address loads -- a wave per (group, slab of 64 16-B columns), NP passes of 64 lanes hold the group's
+// k + m <= 64 * NP entries, the address of the wave-uniform shard id s is a v_readlane (entry_of) --
+// and check_columns for the work.  Every lane loads its entries before anything depends on the lane,
+// and every exit is wave-uniform: past the last group, the plan's status, an id that is not the code's.
+//
+// A shard is exactly `block` bytes with nothing readable after it, so where k_check_apply lets a lane
+// without a column read column 0 and masks the row's last column, here a lane that is not `live` issues
+// no load and carries zero, which every candidate explains; vector work covers whole columns only and
+// needs no mask.  check_columns holds ballots, so it is called by the whole wave: once on 16-B lanes
+// for the slab's whole columns of an aligned group, then over a byte span in steps of 64 on byte lanes:
+// the block % 16 tail on the last slab of an aligned group, the slab's whole span of any other.
+//
+// Aligned is judged from the entries of the unmarked shards alone: bit `lane` of the plan's mark word q
+// belongs to the entry that pass q put in this lane, and a marked entry, which may hold anything and
+// is never dereferenced (the plan lists survivors and spares only), stays out of the ballot.
+template <int NP>
+__global__ void __launch_bounds__(256) k_check_apply_ptrs(CheckPtrsArgs a, const uint64_t* __restrict__ dptrs,
+                                                          const uint64_t* __restrict__ pptrs,
+                                                          const uint8_t* __restrict__ check) {
+    const int lane = threadIdx.x & 63;
+    uint64_t g;
+    uint32_t slab;
+    if (!wave_item(a, &g, &slab)) return;
+    const int k = a.k, m = a.m, n = k + m;
+    const uint8_t* chk = check + g * a.stride;
+    const cptr32 pw = (cptr32)chk;
+    uint64_t p[NP];
+    uint32_t low = 0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        p[q] = 0;
+        if (i < k) p[q] = dptrs[g * (uint64_t)k + i];
+        else if (i < n) p[q] = pptrs[g * (uint64_t)m + (i - k)];
+        const uint64_t marked = pw[QFEC_CHECK_MARKS / 4 + 2 * q] | (uint64_t)pw[QFEC_CHECK_MARKS / 4 + 2 * q + 1] << 32;
+        if (!((marked >> lane) & 1u)) low |= (uint32_t)p[q] & 15u;
+    }
+    const bool aligned = __ballot(low != 0) == 0;
+    const CheckLayout CL = check_layout(k, m);
+    const cptr32 t256 = (cptr32)a.t256;
+    const int S = (int)(pw[0] & 0xFFFFu);
+    if ((pw[1] & 0xFFu) != (uint32_t)QFEC_PLAN_WORK || S < 1 || S > m) return;  // wave-uniform
+    auto columns = [&](auto width, uint64_t off, bool live) {
+        return check_columns<decltype(width)::value>(
+            chk, CL, t256, k, n, S, lane, a.flags + g, a.cmin + g, a.cmax + g,
+            [&](uint32_t s) { return as_row(entry_of<NP>(p, s)); }, off, live);
+    };
+    uint32_t b0 = slab * 1024u, end = std::min((slab + 1) * 1024u, a.block);  // the slab's byte span
+    if (aligned) {
+        const uint32_t col = slab * 64u + lane;
+        if (slab * 64u < a.vcols && !columns(std::integral_constant<int, 4>{}, (uint64_t)col * 16u, col < a.vcols)) return;
+        b0 = slab + 1 == a.wpg ? a.tail0 : end;  // tail0 + tailn = block = end on the last slab
+    }
+#pragma unroll 1
+    for (; b0 < end; b0 += 64)
+        if (!columns(std::integral_constant<int, 1>{}, (uint64_t)b0 + lane, b0 + lane < end)) return;
+}
+
 // one lane per group
 __global__ void __launch_bounds__(256) k_check_finish(CheckFinishArgs a) {
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -300,6 +525,18 @@ hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream) {
     const unsigned grid = (unsigned)((waves + 3) / 4);
     if (a.vec16) hipLaunchKernelGGL((k_check_apply<4>), dim3(grid), dim3(256), 0, stream, a, a.check);
     else hipLaunchKernelGGL((k_check_apply<1>), dim3(grid), dim3(256), 0, stream, a, a.check);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_apply_ptrs(const CheckPtrsArgs& a, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    const uint64_t waves = a.groups * (uint64_t)a.wpg;
+    const int n = a.k + a.m;
+    if (a.wpg == 0 || waves * 64u > 0x7FFFFFFFull || n > 256 || !a.flags || !a.cmin || !a.cmax) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (n <= 64) hipLaunchKernelGGL((k_check_apply_ptrs<1>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
+    else if (n <= 128) hipLaunchKernelGGL((k_check_apply_ptrs<2>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
+    else hipLaunchKernelGGL((k_check_apply_ptrs<4>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
     return hipGetLastError();
 }
 

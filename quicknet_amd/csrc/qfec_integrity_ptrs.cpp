@@ -8,8 +8,7 @@
 
 namespace qfec {
 
-static const char* bad_table_args(const qfec_code* code, unsigned char* const* d_shards, long long groups,
-                                  int block_size) {
+const char* bad_table_args(const qfec_code* code, unsigned char* const* d_shards, long long groups, int block_size) {
     return !code                     ? "null code"
            : groups < 0              ? "groups < 0"
            : block_size < 1          ? "block_size < 1"

@@ -430,6 +430,24 @@ struct CheckApplyArgs {
     int vec16;
 };
 
+// the same on a table of shard addresses (k_check_apply_ptrs): PlanPtrsArgs's mapping and geometry, the
+// check plan and the three words of CheckApplyArgs
+struct CheckPtrsArgs {
+    const uint64_t* dptrs;    // [groups][k] addresses of the data shards of this launch's groups
+    const uint64_t* pptrs;    // [groups][m] addresses of their parity shards
+    const uint8_t* check;     // [groups][stride] of this launch
+    const uint32_t* t256;     // [256][QFEC_TAB_STRIDE] perm tables of every coefficient value
+    unsigned int* flags;      // [groups] of this launch, as in CheckApplyArgs
+    unsigned int* cmin;
+    unsigned int* cmax;
+    uint64_t groups;
+    uint32_t block;           // bytes per shard
+    uint32_t stride;          // CheckLayout::stride
+    uint32_t vcols, wpg;      // whole 16-B columns per shard; waves per group (PtrsGeom at 16-B lanes)
+    uint32_t tail0, tailn;    // the bytes past the last whole column: first byte, count (< 16)
+    int k, m;
+};
+
 // the verdict per group from its check plan's head and its three words
 struct CheckFinishArgs {
     const uint8_t* check;          // [groups][stride] of this launch
@@ -567,6 +585,7 @@ hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply_ptrs_var(const PlanPtrsVarArgs& a, hipStream_t stream);
 hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream);
+hipError_t launch_check_apply_ptrs(const CheckPtrsArgs& a, hipStream_t stream);
 hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);

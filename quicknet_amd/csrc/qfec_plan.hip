@@ -257,27 +257,6 @@ __device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL,
     }
 }
 
-// register s >> 6 of the lane s & 63: entry s of the group's table (s wave-uniform, below 64 * NP)
-template <int NP>
-__device__ __forceinline__ uint64_t entry_of(const uint64_t (&p)[NP], uint32_t s) {
-    const uint32_t l = s & 63u, r = s >> 6;
-    if constexpr (NP == 1) return lane_value(p[0], l);
-    else if constexpr (NP == 2) return r == 0 ? lane_value(p[0], l) : lane_value(p[1], l);
-    else
-        return r == 0 ? lane_value(p[0], l) : r == 1 ? lane_value(p[1], l) : r == 2 ? lane_value(p[2], l) : lane_value(p[3], l);
-}
-template <int NP>
-__device__ __forceinline__ uint32_t entry_of(const uint32_t (&v)[NP], uint32_t s) {
-    const uint32_t l = s & 63u, r = s >> 6;
-    if constexpr (NP == 1) return lane_value32(v[0], l);
-    else if constexpr (NP == 2) return r == 0 ? lane_value32(v[0], l) : lane_value32(v[1], l);
-    else
-        return r == 0   ? lane_value32(v[0], l)
-               : r == 1 ? lane_value32(v[1], l)
-               : r == 2 ? lane_value32(v[2], l)
-                        : lane_value32(v[3], l);
-}
-
 // k_plan_apply_ptrs where every data shard has its own length (qfec_plan_apply_ptrs_var): data shard
 // i of a group is len_i bytes and counts as zero-filled up to the group's length L = glen[g], the
 // length of its parity shards.  Mapping and address loads are k_plan_apply_ptrs's, the launch has

@@ -1,6 +1,6 @@
 // qfec_ptrs_device.hpp -- what the kernels on tables of shard addresses share (qfec_ptrs.hip: encode,
 // reconstruct; qfec_ptrs_var.hip: the same with per-shard lengths; qfec_plan.hip: k_plan_apply_ptrs,
-// k_plan_apply_ptrs_var): reading an address out of the lane that loaded it, saying that it is global
+// k_plan_apply_ptrs_var; qfec_check.hip: k_check_apply_ptrs): reading an address out of the lane that loaded it, saying that it is global
 // memory, a wave's share of its group's shards, the encode's vector body on row addresses, and for
 // the kernels with per-shard lengths a lane's length, the clipped column load and a wave's share of
 // a group that has its own length, the ragged column loads of the templated bodies, and for the integrity
@@ -106,6 +106,28 @@ __device__ __forceinline__ void encode_column(const uint8_t* const (&src)[K], ui
 // v of lane l; l is wave-uniform
 __device__ __forceinline__ uint32_t lane_value32(uint32_t v, uint32_t l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
+
+// register s >> 6 of the lane s & 63: entry s of the group's table (s wave-uniform, below 64 * NP);
+// k_plan_apply_ptrs_var of qfec_plan.hip and k_check_apply_ptrs of qfec_check.hip
+template <int NP>
+__device__ __forceinline__ uint64_t entry_of(const uint64_t (&p)[NP], uint32_t s) {
+    const uint32_t l = s & 63u, r = s >> 6;
+    if constexpr (NP == 1) return lane_value(p[0], l);
+    else if constexpr (NP == 2) return r == 0 ? lane_value(p[0], l) : lane_value(p[1], l);
+    else
+        return r == 0 ? lane_value(p[0], l) : r == 1 ? lane_value(p[1], l) : r == 2 ? lane_value(p[2], l) : lane_value(p[3], l);
+}
+template <int NP>
+__device__ __forceinline__ uint32_t entry_of(const uint32_t (&v)[NP], uint32_t s) {
+    const uint32_t l = s & 63u, r = s >> 6;
+    if constexpr (NP == 1) return lane_value32(v[0], l);
+    else if constexpr (NP == 2) return r == 0 ? lane_value32(v[0], l) : lane_value32(v[1], l);
+    else
+        return r == 0   ? lane_value32(v[0], l)
+               : r == 1 ? lane_value32(v[1], l)
+               : r == 2 ? lane_value32(v[2], l)
+                        : lane_value32(v[3], l);
 }
 
 // the first n < 4 D bytes at q, zero after them: a piece of 8, 4, 2 and 1 bytes per set bit of n, each

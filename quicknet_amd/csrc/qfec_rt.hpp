@@ -23,7 +23,8 @@
 //   qfec_integrity_ptrs_var.cpp  qfec_verify_ptrs_var, qfec_locate_ptrs_var, qfec_scrub_ptrs_var (the same where every
 //                      data shard has its own length; the scrub corrects from one parity row, without a plan)
 //   qfec_check.cpp     qfec_check_build / qfec_check_apply, qfec_locate_wide / qfec_scrub_wide (check plans built
-//                      on the device: single-shard error location at any k + m), qfec_check_build_host
+//                      on the device: single-shard error location at any k + m), qfec_check_build_host,
+//                      qfec_check_apply_ptrs, qfec_locate_ptrs_wide / qfec_scrub_ptrs_wide (the same on a table)
 // Launch geometry (lanes per row, groups per launch) is qfec_geom.hpp's, for every launch site.
 #pragma once
 
@@ -291,6 +292,8 @@ int plan_code_check(const qfec_code* c, const char* who);
 // bad batch argument or nullptr; a plan base the 16-byte stores and dword loads cannot take; the
 // refusal itself, its cause named in the error text (returns QFEC_EINVAL)
 const char* bad_rows_args(const qfec_code* code, long long groups, int block_size, long long pitch);
+// the same for the calls on a table of shard addresses (qfec_integrity_ptrs.cpp); a null table counts with groups > 0
+const char* bad_table_args(const qfec_code* code, unsigned char* const* d_shards, long long groups, int block_size);
 bool plan_misaligned(const void* d_plan);
 int refuse(const char* who, const char* why);
 // one chunk's plans in the one-shot calls stay under this many bytes of stream-ordered scratch
