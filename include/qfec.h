@@ -1003,6 +1003,74 @@ int qfec_scrub_ptrs_wide(qfec_code *code, unsigned char *const *d_shards,
                          int *d_culprit /* nullable */, unsigned int *d_counts /* [5], nullable */,
                          unsigned int *d_failed /* qfec_repair_ptrs_wide's counter, nullable */, void *stream);
 
+/* The same three calls where every data shard has its own length: a receiver's ragged packets, located
+ * and repaired where they lie, at any k + m, beside lost shards or not.  The check plan never refers to a
+ * length, so qfec_check_build and qfec_check_build_host serve these calls unchanged.
+ *   Arguments: table, marks, check plan and accepted codes are qfec_locate_ptrs_wide's (any k + m,
+ *     QFEC_EUNSUP judged on the host); d_lens (groups * k ints in table order), d_group_len (the parity
+ *     length L of each group) and max_len >= 1, which only sizes the launch, are
+ *     qfec_plan_apply_ptrs_var's.
+ *   Judgement per group, in this order.  The plan's status first: status 2 is QFEC_LOC_LOST and its
+ *     lengths are not judged.  For status 0 and 1 alike the lengths come next: L outside [0, max_len],
+ *     or an UNMARKED data shard with len_i outside [0, L] (INT_MIN and INT_MAX included), makes the group
+ *     invalid.  Marked is the plan's mark bit; the d_lens entry of a marked shard is not looked at.  Of
+ *     an invalid group nothing is dereferenced, d_culprit[g] = QFEC_LOC_INVALID, *d_invalid (nullable,
+ *     accumulates) gains 1 exactly once, the group counts nowhere in d_counts and d_marks_out carries the
+ *     input marks as 0 / 1.  A valid group with status 0 is QFEC_LOC_UNCHECKED; a valid group with
+ *     status 1 and L = 0 is QFEC_LOC_CLEAN with nothing dereferenced.
+ *   Reads: a surviving data shard is read in [0, len_i) only and counts as zero up to L; an unmarked
+ *     parity shard is read in [0, L) only; a marked shard is never dereferenced, nor is an unmarked data
+ *     shard with len_i = 0, whose table entry may be anything and takes no part in the alignment
+ *     judgement.  qfec_check_apply_ptrs_var and qfec_locate_ptrs_wide_var write nothing into any shard.
+ *   Verdict: what qfec_check_apply_ptrs gives with block_size = L on the same rows with every data
+ *     survivor zero-padded to L, plus the condition of qfec_locate_ptrs_var: a data shard of K is known
+ *     to be zero in [len_i, L), so it stays a candidate only if every syndrome is zero in every byte
+ *     position >= len_i.  A group whose only padded-rows explanation is a data shard "wrong" past its own
+ *     end is QFEC_LOC_MULTI.  Deviation: with one spare (S = 1) an inconsistent group is
+ *     QFEC_LOC_AMBIGUOUS exactly as in the contiguous call; the lengths are NOT used to narrow that
+ *     verdict, although a damaged byte past the end of all data shards but one could name that one.
+ *   Alignment is judged per group on the device from the entries the call may dereference: the unmarked
+ *     data shards of non-zero length, and the unmarked parity shards when L > 0.  An aligned group runs
+ *     16-byte lanes over its whole columns and its L % 16 tail bytes byte by byte; any other group runs
+ *     byte by byte, much slower.
+ *   qfec_locate_ptrs_wide_var is qfec_check_build into stream-ordered scratch followed by
+ *     qfec_check_apply_ptrs_var, in qfec_locate_ptrs_wide's chunks; d_marks may be NULL and d_marks_out
+ *     may be d_marks itself.  Its marks may be handed to qfec_repair_ptrs_wide_var ONLY where the marked
+ *     culprit has room for L bytes, for that call writes [0, L) of every marked shard.
+ *   qfec_scrub_ptrs_wide_var has no such condition.  It is that locate into stream-ordered scratch marks
+ *     followed by the repair of qfec_repair_ptrs_wide_var: INVALID, MULTI and AMBIGUOUS groups get no
+ *     marks and are untouched byte for byte; LOST groups are untouched and counted into *d_failed;
+ *     UNCHECKED groups, and CLEAN groups with losses, are repaired as qfec_repair_ptrs_wide_var repairs
+ *     them.  Lost shards need room for L bytes and exactly [0, L) of each is written.  A located DATA
+ *     culprit i has exactly its bytes [0, len_i) rewritten and no byte at or past len_i is read or
+ *     written (the shard is known zero there, and a ragged packet buffer has no room there); a located
+ *     parity culprit has [0, L) rewritten.  *d_invalid is the locate's count: once its marks are zeroed
+ *     the repair would judge lengths the caller never promised, so the repair's own count is dropped.
+ *     With all lengths equal to L the result is byte for byte qfec_scrub_ptrs_wide's.
+ *   QFEC_EINVAL, decided on the host before a device is touched, the cause named in qfec_last_error
+ *     after the call's name: a null code, groups < 0, max_len < 1, and with groups > 0 a null d_shards,
+ *     d_lens or d_group_len, a null d_check, for the two locates a null d_culprit; a d_check that is not
+ *     16-byte aligned.  A bad argument wins over groups == 0, which otherwise returns QFEC_OK and
+ *     launches nothing. */
+int qfec_check_apply_ptrs_var(qfec_code *code, unsigned char *const *d_shards,
+                              const int *d_lens /* [groups * k] */, const int *d_group_len /* [groups] */,
+                              const unsigned char *d_check, long long groups, int max_len,
+                              int *d_culprit /* [groups] */, unsigned char *d_marks_out /* nullable */,
+                              unsigned int *d_counts /* [5], nullable */,
+                              unsigned int *d_invalid /* nullable, accumulates */, void *stream);
+int qfec_locate_ptrs_wide_var(qfec_code *code, unsigned char *const *d_shards, const int *d_lens,
+                              const int *d_group_len, const unsigned char *d_marks /* nullable */,
+                              long long groups, int max_len, int *d_culprit /* [groups] */,
+                              unsigned char *d_marks_out /* nullable, may equal d_marks */,
+                              unsigned int *d_counts /* [5], nullable */,
+                              unsigned int *d_invalid /* nullable, accumulates */, void *stream);
+int qfec_scrub_ptrs_wide_var(qfec_code *code, unsigned char *const *d_shards, const int *d_lens,
+                             const int *d_group_len, const unsigned char *d_marks /* nullable */,
+                             long long groups, int max_len, int *d_culprit /* nullable */,
+                             unsigned int *d_counts /* [5], nullable */,
+                             unsigned int *d_failed /* nullable */, unsigned int *d_invalid /* nullable */,
+                             void *stream);
+
 /* The qfec_code behind a handle of the per-call ABIs, so a caller holding fec_new() /
  * reed_solomon_new() handles (e.g. network/FecCodec.cpp's codec list) can batch groups
  * through qfec_encode / qfec_reconstruct with the very same matrix. */

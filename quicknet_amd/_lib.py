@@ -26,6 +26,7 @@ EXPORTS = {
                "qfec_plan_apply_ptrs_var", "qfec_reconstruct_ptrs_wide_var", "qfec_repair_ptrs_wide_var",
                "qfec_check_stride", "qfec_check_build", "qfec_check_apply", "qfec_locate_wide", "qfec_scrub_wide",
                "qfec_check_build_host", "qfec_check_apply_ptrs", "qfec_locate_ptrs_wide", "qfec_scrub_ptrs_wide",
+               "qfec_check_apply_ptrs_var", "qfec_locate_ptrs_wide_var", "qfec_scrub_ptrs_wide_var",
                "qfec_locate","qfec_scrub", "qfec_locate_ratios",
                "qfec_verify_ptrs", "qfec_locate_ptrs", "qfec_scrub_ptrs",
                "qfec_verify_ptrs_var", "qfec_locate_ptrs_var", "qfec_scrub_ptrs_var",
@@ -125,6 +126,9 @@ def lib():
         "qfec_check_apply_ptrs": (i, [vp, vp, vp, ll, i, vp, vp, vp, vp]),
         "qfec_locate_ptrs_wide": (i, [vp, vp, vp, ll, i, vp, vp, vp, vp]),
         "qfec_scrub_ptrs_wide": (i, [vp, vp, vp, ll, i, vp, vp, vp, vp]),
+        "qfec_check_apply_ptrs_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp, vp, vp]),
+        "qfec_locate_ptrs_wide_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp, vp, vp]),
+        "qfec_scrub_ptrs_wide_var": (i, [vp, vp, vp, vp, vp, ll, i, vp, vp, vp, vp, vp]),
         "qfec_locate": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp, vp]),
         "qfec_scrub": (i, [vp, vp, vp, ll, i, ll, vp, vp, vp]),
         "qfec_locate_ratios": (i, [vp, vp]),

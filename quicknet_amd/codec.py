@@ -1008,6 +1008,68 @@ class Code:
                                          _stream_handle(stream)), "qfec_scrub_ptrs_wide")
         return culprit
 
+    def _wide_var_out(self, what, ptrs, lens, group_len, culprit, counts):
+        """_ptrs_out with five counts plus the count and dtype checks of lens [G*k] and group_len [G]."""
+        G, culprit = self._ptrs_out(what, ptrs, culprit, "culprit", counts, 5)
+        self._int32_count(what, "lens", lens, G * self.k)
+        self._int32_count(what, "group_len", group_len, G)
+        return G, culprit
+
+    def check_apply_ptrs_var(self, ptrs, lens, group_len, check_plan, max_len, culprit=None, marks_out=None, counts=None,
+                             invalid=None, stream=None):
+        """check_apply_ptrs() on shards that each have their own length (qfec_check_apply_ptrs_var).  ptrs
+        and check_plan as for check_apply_ptrs(); lens: int32 [G*k] on device (the entries of shards the
+        plans mark are not looked at); group_len: int32 [G] on device, the length of every group's parity
+        shards; max_len only sizes the launch.  A surviving data shard is read below its own length only
+        and counts as zero up to group_len; a group refused for its lengths gets LOC_INVALID.  invalid:
+        optional device int32/uint32 [1] counter of such groups (accumulates).  Returns culprit."""
+        G, culprit = self._wide_var_out("check_apply_ptrs_var", ptrs, lens, group_len, culprit, counts)
+        if check_plan.numel() != G * self.check_stride():
+            raise QfecError(f"check_apply_ptrs_var: check_plan has {check_plan.numel()} bytes for {G} groups of "
+                            f"{self.check_stride()}")
+        self._marks_count("check_apply_ptrs_var", "marks_out", marks_out, G)
+        check(lib().qfec_check_apply_ptrs_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                              _dev_ptr(group_len, _I32, "group_len"),
+                                              _dev_ptr(check_plan, what="check_plan"), G, int(max_len),
+                                              _dev_ptr(culprit, _I32, "culprit"), _dev_ptr(marks_out, what="marks_out"),
+                                              _dev_ptr(counts, _I32, "counts"), _dev_ptr(invalid, _I32, "invalid"),
+                                              _stream_handle(stream)), "qfec_check_apply_ptrs_var")
+        return culprit
+
+    def locate_ptrs_wide_var(self, ptrs, lens, group_len, max_len, marks=None, culprit=None, marks_out=None, counts=None,
+                             invalid=None, stream=None):
+        """locate_ptrs_wide() on shards that each have their own length (qfec_locate_ptrs_wide_var), at
+        any k + m, beside lost shards or not.  lens, group_len, max_len and invalid as for
+        check_apply_ptrs_var(); marks, marks_out and counts as for locate_ptrs_wide().  marks_out is
+        ready for repair_ptrs_wide_var() only where the marked culprit has room for group_len bytes;
+        scrub_ptrs_wide_var() has no such condition.  Returns culprit."""
+        G, culprit = self._wide_var_out("locate_ptrs_wide_var", ptrs, lens, group_len, culprit, counts)
+        self._marks_count("locate_ptrs_wide_var", "marks", marks, G)
+        self._marks_count("locate_ptrs_wide_var", "marks_out", marks_out, G)
+        check(lib().qfec_locate_ptrs_wide_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                              _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(marks, what="marks"), G,
+                                              int(max_len), _dev_ptr(culprit, _I32, "culprit"),
+                                              _dev_ptr(marks_out, what="marks_out"), _dev_ptr(counts, _I32, "counts"),
+                                              _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_locate_ptrs_wide_var")
+        return culprit
+
+    def scrub_ptrs_wide_var(self, ptrs, lens, group_len, max_len, marks=None, culprit=None, counts=None, failed=None,
+                            invalid=None, stream=None):
+        """locate_ptrs_wide_var() and the repair of repair_ptrs_wide_var() in one call
+        (qfec_scrub_ptrs_wide_var): lost shards are rewritten over group_len bytes, a located data shard
+        over exactly its own length, a located parity shard over group_len bytes; INVALID, MULTI,
+        AMBIGUOUS and LOST groups are left as they are.  Returns culprit."""
+        G, culprit = self._wide_var_out("scrub_ptrs_wide_var", ptrs, lens, group_len, culprit, counts)
+        self._marks_count("scrub_ptrs_wide_var", "marks", marks, G)
+        check(lib().qfec_scrub_ptrs_wide_var(self._h, _dev_ptr(ptrs, _I64, "ptrs"), _dev_ptr(lens, _I32, "lens"),
+                                             _dev_ptr(group_len, _I32, "group_len"), _dev_ptr(marks, what="marks"), G,
+                                             int(max_len), _dev_ptr(culprit, _I32, "culprit"),
+                                             _dev_ptr(counts, _I32, "counts"), _dev_ptr(failed, _I32, "failed"),
+                                             _dev_ptr(invalid, _I32, "invalid"), _stream_handle(stream)),
+              "qfec_scrub_ptrs_wide_var")
+        return culprit
+
     # -- FEC datagram batches (network/FecCodecBuf.cpp wire format); n = k + m <= 15
     def pack_datagrams(self, payload, offsets, sizes, seq, checksum=True, shard_pitch=None, wire_pitch=None,
                        stream=None):

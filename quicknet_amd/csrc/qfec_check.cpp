@@ -2,7 +2,9 @@
 // qfec_check_build, qfec_check_apply, the one-shot calls qfec_locate_wide (build into stream-ordered
 // scratch, then apply) and qfec_scrub_wide (locate into scratch marks, then qfec_repair_wide), and
 // the host query qfec_check_build_host; and the same on a table of shard addresses: qfec_check_apply_ptrs,
-// qfec_locate_ptrs_wide and qfec_scrub_ptrs_wide (then qfec_repair_ptrs_wide).
+// qfec_locate_ptrs_wide and qfec_scrub_ptrs_wide (then qfec_repair_ptrs_wide); and with a length per shard:
+// qfec_check_apply_ptrs_var, qfec_locate_ptrs_wide_var and qfec_scrub_ptrs_wide_var (then the repair of
+// qfec_repair_ptrs_wide_var with the located shard written up to its own length).
 // The check plan of a group is computed from its marks on the device (qfec_check.hip) by the arithmetic of qfec_plan.hpp: no LUT, no record per mask, no
 // read-back and no k + m limit.  Arguments and the code are judged on the host before a device is
 // touched.
@@ -101,11 +103,12 @@ static CheckGeom check_geom(DevCtx& ctx, const qfec_code* c, const uint8_t* d_da
 
 // the launches over groups [g0, g0 + gn) of a batch of `groups`, whose check plans start at d_check:
 // three presets, the main kernel per chunk of `per` groups -- launch(c0, cn, flags, cmin, cmax), the
-// words being those of group g0 -- and the finish kernel.  d_culprit is the batch's.
+// words being those of group g0 -- and the finish kernel.  d_culprit is the batch's.  var: the finish
+// kernel that knows an invalid group and counts it into d_invalid (nullable).
 template <class Launch>
 static int run_check_words(const qfec_code* c, uint32_t stride, long long per, const uint8_t* d_check, long long g0,
                            long long gn, long long groups, int* d_culprit, uint8_t* d_marks_out, unsigned* d_counts,
-                           int scrub, hipStream_t s, Launch&& launch) {
+                           int scrub, hipStream_t s, Launch&& launch, bool var = false, unsigned* d_invalid = nullptr) {
     GroupWords words(s);  // [gn] flags, lowest candidate, highest candidate
     int rc = words.init("check_apply", gn, 3);
     if (rc) return rc;
@@ -130,7 +133,7 @@ static int run_check_words(const qfec_code* c, uint32_t stride, long long per, c
     f.k = c->k;
     f.m = c->m;
     f.scrub = scrub;
-    const hipError_t e = launch_check_finish(f, s);
+    const hipError_t e = var ? launch_check_finish_var(f, d_invalid, s) : launch_check_finish(f, s);
     return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_finish kernel launch");
 }
 
@@ -181,6 +184,40 @@ static int run_check_apply_ptrs(DevCtx& ctx, const qfec_code* c, const uint64_t*
                            });
 }
 
+// the same with per-shard lengths: lens / glen are the batch's d_lens and d_group_len
+static int run_check_apply_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
+                                    const int32_t* lens, const int32_t* glen, const uint8_t* d_check, long long g0,
+                                    long long gn, long long groups, int max_len, int* d_culprit, uint8_t* d_marks_out,
+                                    unsigned* d_counts, unsigned* d_invalid, int scrub, hipStream_t s) {
+    CheckPtrsVarArgs a{};
+    const PtrsGeom p = ptrs_geom(max_len, 16);
+    a.p.t256 = ctx.d_t256;
+    a.p.k = c->k;
+    a.p.m = c->m;
+    a.p.block = (uint32_t)max_len;
+    a.p.stride = (uint32_t)check_layout(c->k, c->m).stride;
+    a.p.vcols = p.vcols;
+    a.p.wpg = p.wpg;
+    a.p.tail0 = p.tail0;
+    a.p.tailn = p.tailn;
+    return run_check_words(
+        c, a.p.stride, p.per, d_check, g0, gn, groups, d_culprit, d_marks_out, d_counts, scrub, s,
+        [&](long long c0, long long cn, unsigned* flags, unsigned* cmin, unsigned* cmax) {
+            a.p.dptrs = dptrs + (size_t)(g0 + c0) * a.p.k;
+            a.p.pptrs = pptrs + (size_t)(g0 + c0) * a.p.m;
+            a.lens = lens + (size_t)(g0 + c0) * a.p.k;
+            a.group_len = glen + (g0 + c0);
+            a.p.check = d_check + (size_t)c0 * a.p.stride;
+            a.p.flags = flags;
+            a.p.cmin = cmin;
+            a.p.cmax = cmax;
+            a.p.groups = (uint64_t)cn;
+            const hipError_t e = launch_check_apply_ptrs_var(a, s);
+            return e == hipSuccess ? QFEC_OK : hip_fail(e, "check_apply_ptrs_var kernel launch");
+        },
+        true, d_invalid);
+}
+
 // the one-shot locates: per chunk, check plans into stream-ordered scratch, apply(g0, gn, plans), free
 template <class Apply>
 static int locate_wide_chunks(const char* who, DevCtx& ctx, qfec_code* code, const uint8_t* d_marks, long long groups,
@@ -218,6 +255,29 @@ static int run_locate_ptrs_wide(const char* who, DevCtx& ctx, qfec_code* code, c
         return run_check_apply_ptrs(ctx, code, t, t + (size_t)groups * code->k, chk, g0, gn, groups, block_size, d_culprit,
                                     d_marks_out, d_counts, scrub, s);
     });
+}
+
+// qfec_locate_ptrs_wide_var
+static int run_locate_ptrs_wide_var(const char* who, DevCtx& ctx, qfec_code* code, const uint64_t* t, const int32_t* lens,
+                                    const int32_t* glen, const uint8_t* d_marks, long long groups, int max_len,
+                                    int* d_culprit, uint8_t* d_marks_out, unsigned* d_counts, unsigned* d_invalid,
+                                    int scrub, hipStream_t s) {
+    return locate_wide_chunks(who, ctx, code, d_marks, groups, s, [&](long long g0, long long gn, const uint8_t* chk) {
+        return run_check_apply_ptrs_var(ctx, code, t, t + (size_t)groups * code->k, lens, glen, chk, g0, gn, groups,
+                                        max_len, d_culprit, d_marks_out, d_counts, d_invalid, scrub, s);
+    });
+}
+
+// what the three calls with per-shard lengths refuse before anything else
+static const char* bad_table_var_args(const qfec_code* code, unsigned char* const* d_shards, const int* d_lens,
+                                      const int* d_group_len, long long groups, int max_len) {
+    return !code                        ? "null code"
+           : groups < 0                 ? "groups < 0"
+           : max_len < 1                ? "max_len < 1"
+           : groups > 0 && !d_shards    ? "null d_shards"
+           : groups > 0 && !d_lens      ? "null d_lens"
+           : groups > 0 && !d_group_len ? "null d_group_len"
+                                        : nullptr;
 }
 
 }  // namespace qfec
@@ -363,6 +423,64 @@ int qfec_scrub_ptrs_wide(qfec_code* code, unsigned char* const* d_shards, const 
     rc = run_locate_ptrs_wide(who, *ctx, code, reinterpret_cast<const uint64_t*>(d_shards), d_marks, groups, block_size,
                               d_culprit, marks, d_counts, 1, s);
     if (!rc) rc = qfec_repair_ptrs_wide(code, d_shards, marks, groups, block_size, d_failed, stream);
+    (void)hipFreeAsync(marks, s);
+    return rc;
+}
+
+int qfec_check_apply_ptrs_var(qfec_code* code, unsigned char* const* d_shards, const int* d_lens, const int* d_group_len,
+                              const unsigned char* d_check, long long groups, int max_len, int* d_culprit,
+                              unsigned char* d_marks_out, unsigned int* d_counts, unsigned int* d_invalid, void* stream) {
+    const char* who = "qfec_check_apply_ptrs_var";
+    const char* why = bad_table_var_args(code, d_shards, d_lens, d_group_len, groups, max_len);
+    if (!why && groups > 0) why = !d_check ? "null d_check" : !d_culprit ? "null d_culprit" : nullptr;
+    if (!why && plan_misaligned(d_check)) why = "d_check not 16-byte aligned";
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    const int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    const uint64_t* t = reinterpret_cast<const uint64_t*>(d_shards);
+    return run_check_apply_ptrs_var(*ctx, code, t, t + (size_t)groups * code->k, d_lens, d_group_len, d_check, 0, groups,
+                                    groups, max_len, d_culprit, d_marks_out, d_counts, d_invalid, 0, (hipStream_t)stream);
+}
+
+int qfec_locate_ptrs_wide_var(qfec_code* code, unsigned char* const* d_shards, const int* d_lens, const int* d_group_len,
+                              const unsigned char* d_marks, long long groups, int max_len, int* d_culprit,
+                              unsigned char* d_marks_out, unsigned int* d_counts, unsigned int* d_invalid, void* stream) {
+    const char* who = "qfec_locate_ptrs_wide_var";
+    const char* why = bad_table_var_args(code, d_shards, d_lens, d_group_len, groups, max_len);
+    if (!why && groups > 0 && !d_culprit) why = "null d_culprit";
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    const int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    return run_locate_ptrs_wide_var(who, *ctx, code, reinterpret_cast<const uint64_t*>(d_shards), d_lens, d_group_len,
+                                    d_marks, groups, max_len, d_culprit, d_marks_out, d_counts, d_invalid, 0,
+                                    (hipStream_t)stream);
+}
+
+int qfec_scrub_ptrs_wide_var(qfec_code* code, unsigned char* const* d_shards, const int* d_lens, const int* d_group_len,
+                             const unsigned char* d_marks, long long groups, int max_len, int* d_culprit,
+                             unsigned int* d_counts, unsigned int* d_failed, unsigned int* d_invalid, void* stream) {
+    const char* who = "qfec_scrub_ptrs_wide_var";
+    const char* why = bad_table_var_args(code, d_shards, d_lens, d_group_len, groups, max_len);
+    if (why) return refuse(who, why);
+    DevCtx* ctx = nullptr;
+    int rc = batch_begin(who, false, [&] { return check_code_check(code, who); }, groups == 0, &ctx);
+    if (rc || !ctx) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t* t = reinterpret_cast<const uint64_t*>(d_shards);
+    // the locate's marks_out, then the repair's marks; behind them (4-byte aligned) the verdicts the repair's
+    // write clip reads, where the caller wants none
+    const size_t nmarks = ((size_t)groups * (size_t)(code->k + code->m) + 3) & ~(size_t)3;
+    uint8_t* marks = nullptr;
+    if (hipMallocAsync((void**)&marks, nmarks + (d_culprit ? 0 : (size_t)groups * sizeof(int)), s) != hipSuccess)
+        return hip_fail(hipGetLastError(), "scrub_ptrs_wide_var scratch");
+    int* culprit = d_culprit ? d_culprit : reinterpret_cast<int*>(marks + nmarks);
+    rc = run_locate_ptrs_wide_var(who, *ctx, code, t, d_lens, d_group_len, d_marks, groups, max_len, culprit, marks,
+                                  d_counts, d_invalid, 1, s);
+    if (!rc)
+        rc = run_repair_ptrs_wide_var_clip(*ctx, code, t, d_lens, d_group_len, marks, culprit, groups, max_len, d_failed, s,
+                                           who);
     (void)hipFreeAsync(marks, s);
     return rc;
 }

@@ -29,6 +29,11 @@
 // k_check_apply_ptrs: the same arithmetic and cold path (check_columns) where the rows are given by a
 // device table of shard addresses (qfec_check_apply_ptrs), in the mapping of k_plan_apply_ptrs; the
 // words and the finish kernel are the same.
+//
+// k_check_apply_ptrs_var: the same where every data shard has its own length (qfec_check_apply_ptrs_var),
+// with the lengths and the per-group geometry of k_plan_apply_ptrs_var; a wave whose data survivors all
+// reach the end of its span runs check_columns unchanged, any other with clipped loads and the length
+// condition (RaggedRows).  k_check_finish_var is the finish kernel that knows an invalid group.
 #include <type_traits>
 
 #include "../../include/qfec.h"
@@ -263,17 +268,42 @@ __global__ void __launch_bounds__(256) k_check_apply(CheckApplyArgs a, const uin
 // The call is wave-uniform (ballots and readlane inside) and folds what it finds into the group's
 // three words.  False: not a check plan of this code, nothing more to do.
 // (The two bodies stay apart: as one function this text moved k_check_apply<4>'s SGPR count.)
-template <int D, class Row>
+//
+// Len (k_check_apply_ptrs_var's ragged waves; WholeRows: none of this): shard s may be read in
+// [0, len.of(s)) only and counts as zero from there on, so a live lane's load is clipped to it (ldv_clip:
+// the whole column, its first bytes in pieces, or nothing and then no load), and a data shard is known
+// to be zero from its own end on: a candidate of K that is a data shard is rejected where a byte of the
+// wave at or past its length has a non-zero first syndrome, byte-exact inside a 16-B lane.  (The
+// candidate passed the ratio test, so where its first syndrome is zero every syndrome is.)
+struct WholeRows {
+    static constexpr bool ragged = false;
+};
+template <class F>
+struct RaggedRows {
+    static constexpr bool ragged = true;
+    F of;
+};
+
+template <int D, class Row, class Len = WholeRows>
 __device__ __forceinline__ bool check_columns(const uint8_t* chk, const CheckLayout& CL, cptr32 t256, int k, int n, int S,
                                               int lane, unsigned int* flags, unsigned int* cmin, unsigned int* cmax,
-                                              const Row& row, uint64_t off, bool live) {
+                                              const Row& row, uint64_t off, bool live, const Len& len = Len{}) {
     static_assert(D == 4 || D == 1, "16-B columns or bytes");
     const cptr32 pw = (cptr32)chk;
     auto ld = [&](uint32_t(&v)[D], uint32_t s) {
         const uint8_t* r = row(s);  // every lane takes part in the readlane
 #pragma unroll
         for (int d = 0; d < D; ++d) v[d] = 0;
-        if (live) check_ld<D>(v, r + off);
+        if constexpr (Len::ragged) {
+            const uint32_t end = len.of(s);  // a readlane as well
+            if constexpr (D == 4) {
+                if (live) ldv_clip<4>(v, r, (uint32_t)off, end);
+            } else {
+                if (live && (uint32_t)off < end) v[0] = r[off];
+            }
+        } else {
+            if (live) check_ld<D>(v, r + off);
+        }
     };
     uint32_t s0[D];  // the first spare's syndrome, from pass 0
 #pragma unroll
@@ -400,6 +430,23 @@ __device__ __forceinline__ bool check_columns(const uint8_t* chk, const CheckLay
                     for (int d = 0; d < D; ++d) ok = ok && acc[j][d] == 0;
                 }
             }
+        if constexpr (Len::ragged) {
+            if (kind == KPOS) {
+                const uint32_t id = check_u8(pw, QFEC_CHECK_IDS + cpos);
+                if (id < (uint32_t)k) {  // wave-uniform
+                    const uint32_t end = len.of(id);
+#pragma unroll
+                    for (int d = 0; d < D; ++d) {
+                        const uint32_t at = (uint32_t)off + 4u * d;  // the bytes at or past `end` of this dword
+                        const uint32_t past = D == 1 ? (at >= end ? 0xFFu : 0u)
+                                              : at >= end    ? 0xFFFFFFFFu
+                                              : end - at >= 4u ? 0u
+                                                               : 0xFFFFFFFFu << (8u * (end - at));
+                        ok = ok && (s0[d] & past) == 0;
+                    }
+                }
+            }
+        }
         const bool all_ok = kind != NONE && __ballot(!ok) == 0;
         if (lane == 0) {
             atomicOr(flags, all_ok ? 1u : 3u);
@@ -474,6 +521,110 @@ __global__ void __launch_bounds__(256) k_check_apply_ptrs(CheckPtrsArgs a, const
         if (!columns(std::integral_constant<int, 1>{}, (uint64_t)b0 + lane, b0 + lane < end)) return;
 }
 
+// k_check_apply_ptrs where every data shard has its own length (qfec_check_apply_ptrs_var): data shard i
+// of a group is len_i bytes and counts as zero-filled up to the group's length L = glen[g], the length
+// of its parity shards.  Mapping and address loads are k_check_apply_ptrs's; the launch has
+// ptrs_geom(max_len, 16).wpg waves per group.  New here:
+//
+// Lengths.  A lane loads its entry's length in the same round trip as the address; with L, a scalar
+// load, that makes NP registers of readable length (len_i of a data shard, L of a parity shard), read
+// where they are used with readlane, like the addresses.  Every lane executes these loads before the
+// first lane-dependent branch; every exit is wave-uniform: past the last group, a failed plan or none
+// of this code, invalid lengths, a plan without work, an empty group, a slab at or past L, an id that
+// is not the code's.
+//
+// Judgement.  After the plan's status (failed: nothing is judged) and for status 0 and 1 alike: L
+// outside [0, max_len] or an unmarked data shard outside [0, L] makes the group invalid.  Marked is
+// the plan's mark bit; the length of a marked shard is not looked at.  Every wave judges (a ballot),
+// slab 0 alone reports: bit 2 of the group's flags, which k_check_finish_var turns into the verdict.
+//
+// Alignment is judged on the entries the wave may dereference: the unmarked shards of non-zero length
+// (L > 0 here, so every unmarked parity shard).  The group cuts its own geometry, ptrs_var_geom(L, 16).
+// Every unmarked data shard belongs to K (the k lowest unmarked ids), so a wave all of whose unmarked
+// data shards reach the end of its span is `full` and runs k_check_apply_ptrs's body unchanged with
+// block = L (all lengths equal: every wave); any other wave runs the same calls with RaggedRows.
+template <int NP>
+__global__ void __launch_bounds__(256) k_check_apply_ptrs_var(CheckPtrsVarArgs a, const uint64_t* __restrict__ dptrs,
+                                                              const uint64_t* __restrict__ pptrs,
+                                                              const int32_t* __restrict__ lens,
+                                                              const int32_t* __restrict__ glen,
+                                                              const uint8_t* __restrict__ check) {
+    const int lane = threadIdx.x & 63;
+    uint64_t g;
+    uint32_t slab;
+    if (!wave_item(a.p, &g, &slab)) return;
+    const int k = a.p.k, m = a.p.m, n = k + m;
+    const uint8_t* chk = check + g * a.p.stride;
+    const cptr32 pw = (cptr32)chk;
+    uint64_t p[NP];
+    uint32_t eff[NP];  // as unsigned: a negative length is above every L
+    bool un[NP];       // an unmarked shard of the code
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        p[q] = 0;
+        eff[q] = 0;
+        if (i < k) {
+            p[q] = dptrs[g * (uint64_t)k + i];
+            eff[q] = (uint32_t)lens[g * (uint64_t)k + i];
+        } else if (i < n) {
+            p[q] = pptrs[g * (uint64_t)m + (i - k)];
+        }
+        const uint64_t marked = pw[QFEC_CHECK_MARKS / 4 + 2 * q] | (uint64_t)pw[QFEC_CHECK_MARKS / 4 + 2 * q + 1] << 32;
+        un[q] = i < n && !((marked >> lane) & 1u);
+    }
+    const uint32_t L = (uint32_t)glen[g];
+    const CheckLayout CL = check_layout(k, m);
+    const cptr32 t256 = (cptr32)a.p.t256;
+    const int S = (int)(pw[0] & 0xFFFFu);
+    const uint32_t status = pw[1] & 0xFFu;
+    if (status > (uint32_t)QFEC_PLAN_WORK || (status == (uint32_t)QFEC_PLAN_WORK && (S < 1 || S > m))) return;  // wave-uniform
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = q * 64 + lane;
+        bad |= un[q] && i < k && eff[q] > L;
+        if (i >= k && i < n) eff[q] = L;
+    }
+    if (L > a.p.block || __ballot(bad)) {  // invalid: nothing dereferenced, reported once
+        if (slab == 0 && lane == 0) atomicOr(a.p.flags + g, 4u);
+        return;
+    }
+    const PtrsVarGeom v = ptrs_var_geom(L, 16);
+    if (status != (uint32_t)QFEC_PLAN_WORK || slab >= v.live) return;  // unchecked, an empty group, a slab at or past L
+    const uint32_t end = std::min((slab + 1) * 1024u, L);  // the slab's byte span ends here
+    bool low = false, cut = false;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        low |= un[q] && eff[q] != 0 && ((uint32_t)p[q] & 15u) != 0;
+        cut |= un[q] && eff[q] < end;  // a parity shard's is L
+    }
+    const bool aligned = __ballot(low) == 0;
+    const bool full = __ballot(cut) == 0;
+    auto row = [&](uint32_t s) { return as_row(entry_of<NP>(p, s)); };
+    auto span = [&](const auto& rows) {
+        auto columns = [&](auto width, uint64_t off, bool live) {
+            return check_columns<decltype(width)::value>(chk, CL, t256, k, n, S, lane, a.p.flags + g, a.p.cmin + g,
+                                                         a.p.cmax + g, row, off, live, rows);
+        };
+        uint32_t b0 = slab * 1024u;
+        if (aligned) {
+            const uint32_t col = slab * 64u + lane;
+            if (slab * 64u < v.vcols && !columns(std::integral_constant<int, 4>{}, (uint64_t)col * 16u, col < v.vcols)) return;
+            b0 = slab + 1 == v.live ? v.tail0 : end;  // tail0 + tailn = L = end on the last live slab
+        }
+#pragma unroll 1
+        for (; b0 < end; b0 += 64)
+            if (!columns(std::integral_constant<int, 1>{}, (uint64_t)b0 + lane, b0 + lane < end)) return;
+    };
+    if (full) {
+        span(WholeRows{});
+    } else {
+        auto of = [&](uint32_t s) -> uint32_t { return entry_of<NP>(eff, s); };
+        span(RaggedRows<decltype(of)>{of});
+    }
+}
+
 // one lane per group
 __global__ void __launch_bounds__(256) k_check_finish(CheckFinishArgs a) {
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -511,6 +662,49 @@ __global__ void __launch_bounds__(256) k_check_finish(CheckFinishArgs a) {
     if (a.counts) block_counts<5>(verdict, a.counts);  // uniform over the grid
 }
 
+// k_check_finish for k_check_apply_ptrs_var, whose flags know bit 2: the group's lengths are out of range.
+// Judged after a failed plan and before everything else; QFEC_LOC_INVALID counts in no entry of counts
+// and once in *invalid, its marks are the input marks (scrub: none).  (A kernel of its own: as one
+// body with a switch this text moved k_check_finish's SGPR count.)
+__global__ void __launch_bounds__(256) k_check_finish_var(CheckFinishArgs a, unsigned int* invalid) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    int verdict = -1, bad = -1;  // also for lanes past the last group
+    if (g < a.groups) {
+        const uint32_t* pw = reinterpret_cast<const uint32_t*>(a.check + g * a.stride);
+        const int S = (int)(pw[0] & 0xFFFFu);
+        const uint32_t status = pw[1] & 0xFFu;
+        uint64_t mk[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) mk[w] = pw[4 + 2 * w] | (uint64_t)pw[5 + 2 * w] << 32;
+        const uint32_t flags = a.flags[g];
+        int id = QFEC_LOC_CLEAN;
+        if (status == (uint32_t)QFEC_PLAN_FAILED) {
+            id = QFEC_LOC_LOST;
+        } else if (flags & 4u) {
+            id = QFEC_LOC_INVALID;
+        } else if (status == (uint32_t)QFEC_PLAN_NONE) {
+            id = QFEC_LOC_UNCHECKED;
+        } else if (flags != 0) {
+            if (S == 1) id = QFEC_LOC_AMBIGUOUS;
+            else if ((flags & 2u) || a.cmin[g] != a.cmax[g]) id = QFEC_LOC_MULTI;
+            else id = (int)a.cmin[g];
+        }
+        if (a.culprit) a.culprit[g] = id;
+        if (a.marks_out) {
+            const bool none = a.scrub && (id == QFEC_LOC_MULTI || id == QFEC_LOC_AMBIGUOUS || id == QFEC_LOC_INVALID);
+            const int k = a.k, m = a.m;
+            uint8_t* dm = a.marks_out + (a.g0 + g) * (uint64_t)k;
+            uint8_t* pm = a.marks_out + a.all_groups * (uint64_t)k + (a.g0 + g) * (uint64_t)m;
+            for (int i = 0; i < k; ++i) dm[i] = none ? 0 : (uint8_t)(plan_bit(mk, i) | (i == id));
+            for (int j = 0; j < m; ++j) pm[j] = none ? 0 : (uint8_t)(plan_bit(mk, k + j) | (k + j == id));
+        }
+        bad = id == QFEC_LOC_INVALID ? 0 : -1;
+        verdict = id >= 0 ? 0 : id == QFEC_LOC_CLEAN || id == QFEC_LOC_INVALID ? -1 : -id - 1;
+    }
+    if (a.counts) block_counts<5>(verdict, a.counts);  // uniform over the grid
+    if (invalid) block_counts<1>(bad, invalid);
+}
+
 hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream) {
     if (a.groups == 0) return hipSuccess;
     if (a.groups > 0x7FFFFFFFull / 64u || a.lds > 65536u) return hipErrorInvalidValue;  // caller chunks
@@ -537,6 +731,34 @@ hipError_t launch_check_apply_ptrs(const CheckPtrsArgs& a, hipStream_t stream) {
     if (n <= 64) hipLaunchKernelGGL((k_check_apply_ptrs<1>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
     else if (n <= 128) hipLaunchKernelGGL((k_check_apply_ptrs<2>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
     else hipLaunchKernelGGL((k_check_apply_ptrs<4>), dim3(grid), dim3(256), 0, stream, a, a.dptrs, a.pptrs, a.check);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_apply_ptrs_var(const CheckPtrsVarArgs& a, hipStream_t stream) {
+    if (a.p.groups == 0) return hipSuccess;
+    const uint64_t waves = a.p.groups * (uint64_t)a.p.wpg;
+    const int n = a.p.k + a.p.m;
+    if (a.p.wpg != ptrs_geom((int)a.p.block, 16).wpg || waves * 64u > 0x7FFFFFFFull || n > 256 || !a.p.flags || !a.p.cmin ||
+        !a.p.cmax || !a.lens || !a.group_len)
+        return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (n <= 64)
+        hipLaunchKernelGGL((k_check_apply_ptrs_var<1>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.check);
+    else if (n <= 128)
+        hipLaunchKernelGGL((k_check_apply_ptrs_var<2>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.check);
+    else
+        hipLaunchKernelGGL((k_check_apply_ptrs_var<4>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
+                           a.group_len, a.p.check);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_finish_var(const CheckFinishArgs& a, unsigned int* invalid, hipStream_t stream) {
+    if (a.groups == 0) return hipSuccess;
+    if (!a.check || !a.flags || !a.cmin || !a.cmax || a.groups > 0x7FFFFFFFull * 256u) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((a.groups + 255) / 256);
+    hipLaunchKernelGGL(k_check_finish_var, dim3(grid), dim3(256), 0, stream, a, invalid);
     return hipGetLastError();
 }
 

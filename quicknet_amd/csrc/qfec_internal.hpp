@@ -448,6 +448,15 @@ struct CheckPtrsArgs {
     int k, m;
 };
 
+// the same with per-shard lengths (k_check_apply_ptrs_var): p with block = max_len and the geometry of
+// max_len, which only sizes the launch; every group cuts its own length inside the kernel (ptrs_var_geom).
+// An invalid group sets bit 2 (value 4) of its flags word and nothing else
+struct CheckPtrsVarArgs {
+    CheckPtrsArgs p;
+    const int32_t* lens;         // [groups][k] lengths of the data shards of this launch's groups
+    const int32_t* group_len;    // [groups] length of the group's parity shards
+};
+
 // the verdict per group from its check plan's head and its three words
 struct CheckFinishArgs {
     const uint8_t* check;          // [groups][stride] of this launch
@@ -583,10 +592,14 @@ hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply(const PlanApplyArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply_ptrs(const PlanPtrsArgs& a, hipStream_t stream);
 hipError_t launch_plan_apply_ptrs_var(const PlanPtrsVarArgs& a, hipStream_t stream);
+hipError_t launch_plan_apply_ptrs_var_clip(const PlanPtrsVarArgs& a, const int32_t* culprit, hipStream_t stream);
 hipError_t launch_check_build(const PlanBuildArgs& a, hipStream_t stream);
 hipError_t launch_check_apply(const CheckApplyArgs& a, hipStream_t stream);
 hipError_t launch_check_apply_ptrs(const CheckPtrsArgs& a, hipStream_t stream);
 hipError_t launch_check_finish(const CheckFinishArgs& a, hipStream_t stream);
+hipError_t launch_check_apply_ptrs_var(const CheckPtrsVarArgs& a, hipStream_t stream);
+// invalid: counter of the groups whose flags say invalid; may be NULL
+hipError_t launch_check_finish_var(const CheckFinishArgs& a, unsigned int* invalid, hipStream_t stream);
 hipError_t launch_synth_fill(uint8_t* p, uint64_t nbytes, uint64_t seed, hipStream_t stream);
 hipError_t launch_probe_xor(const EncodeArgs& a, hipStream_t stream);
 hipError_t launch_probe_recon(const ReconArgs& a, hipStream_t stream);

@@ -19,6 +19,9 @@
 // k_plan_apply_ptrs_var: the same where every data shard has its own length (qfec_plan_apply_ptrs_var),
 // with the lengths, the per-group geometry and the clipped loads of qfec_ptrs_var.hip; a wave whose
 // survivors all reach its columns runs plan_column unchanged, any other plan_column_var.
+//
+// k_plan_apply_ptrs_var_clip: the same wave where one listed data shard per group, the shard a locate
+// found, is written up to its own length only (the repair of qfec_scrub_ptrs_wide_var).
 #include "qfec_device.hpp"
 #include "qfec_geom.hpp"
 #include "qfec_plan.hpp"
@@ -196,10 +199,27 @@ __global__ void __launch_bounds__(256) k_plan_apply_ptrs(PlanPtrsArgs a, const u
 // a survivor's 16 bytes at `off` come through ldv_clip -- the whole column, its first bytes in pieces
 // of 8, 4, 2 and 1, or nothing and then no load; else byte `off`, read when it lies below eff(s).  The
 // listed rows are whole in [0, L) and `off` lies inside it: the stale loads and the stores are
-// plan_column's.
-template <bool VEC16, class Row, class Eff>
+// plan_column's.  Room (k_plan_apply_ptrs_var_clip only): listed row l has room(l) <= L bytes, and no
+// byte at or past them is read or written.
+struct WholeRoom {
+    static constexpr bool clips = false;
+};
+template <class F>
+struct ClippedRoom {
+    static constexpr bool clips = true;
+    F of;
+};
+
+// the first n < 16 bytes of v to q, byte by byte: one lane of one located shard per call
+__device__ __forceinline__ void st16_part(uint8_t* q, const uint4& v, uint32_t n) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll 1
+    for (uint32_t b = 0; b < n; ++b) q[b] = (uint8_t)(w[b >> 2] >> (8u * (b & 3u)));
+}
+
+template <bool VEC16, class Row, class Eff, class Room = WholeRoom>
 __device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL, cptr32 t256, int k, int n, int t,
-                                                const Row& row, const Eff& eff, uint32_t off) {
+                                                const Row& row, const Eff& eff, uint32_t off, const Room& room = Room{}) {
     using Acc = typename std::conditional<VEC16, uint4, uint32_t>::type;
 
     for (int j0 = 0; j0 < t; j0 += PCH) {
@@ -208,7 +228,16 @@ __device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL,
         for (int j = 0; j < PCH; ++j) {
             const int jj = j0 + j;
             const bool stale = jj < t && plan_u8(pw, PL.stale_off + jj) != 0;
-            if constexpr (VEC16) {
+            if constexpr (Room::clips) {
+                const uint32_t l = plan_u8(pw, PL.lost_off + jj);
+                if constexpr (VEC16) {
+                    acc[j] = make_uint4(0, 0, 0, 0);
+                    if (stale) acc[j] = ld16_clip(row(l), off, room.of(l));
+                } else {
+                    acc[j] = 0;
+                    if (stale && off < room.of(l)) acc[j] = row(l)[off];
+                }
+            } else if constexpr (VEC16) {
                 acc[j] = make_uint4(0, 0, 0, 0);
                 if (stale) acc[j] = *reinterpret_cast<const uint4*>(row(plan_u8(pw, PL.lost_off + jj)) + off);
             } else {
@@ -251,7 +280,15 @@ __device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL,
             if (j0 + j < t) {
                 const uint32_t l = plan_u8(pw, PL.lost_off + j0 + j);
                 if (l >= (uint32_t)n) continue;
-                if constexpr (VEC16) st16(row(l) + off, acc[j]);
+                if constexpr (Room::clips) {
+                    const uint32_t end = room.of(l);
+                    if constexpr (VEC16) {
+                        if (off + 16u <= end) st16(row(l) + off, acc[j]);
+                        else if (off < end) st16_part(row(l) + off, acc[j], end - off);
+                    } else {
+                        if (off < end) row(l)[off] = (uint8_t)acc[j];
+                    }
+                } else if constexpr (VEC16) st16(row(l) + off, acc[j]);
                 else row(l)[off] = (uint8_t)acc[j];
             }
     }
@@ -279,12 +316,18 @@ __device__ __forceinline__ void plan_column_var(cptr32 pw, const PlanLayout& PL,
 // slab_reach<16> runs plan_column<true> unchanged (with all lengths equal: every wave); any other
 // wave runs plan_column_var<true>.  The tail of an aligned group and every byte of a misaligned one
 // run plan_column_var<false>.
-template <int NP>
-__global__ void __launch_bounds__(256) k_plan_apply_ptrs_var(PlanPtrsVarArgs a, const uint64_t* __restrict__ dptrs,
-                                                             const uint64_t* __restrict__ pptrs,
-                                                             const int32_t* __restrict__ lens,
-                                                             const int32_t* __restrict__ glen,
-                                                             const uint8_t* __restrict__ plan) {
+//
+// CLIP (k_plan_apply_ptrs_var_clip, the repair of qfec_scrub_ptrs_wide_var): culprit[g] in [0, k) names a
+// listed data shard that has room for its own length only, the d_lens entry the locate judged.  Its
+// stale load and its stores stop there (ClippedRoom), and a wave is `full` only where that shard
+// reaches the wave's columns as well.  Any other value of culprit[g] clips nothing.
+template <int NP, bool CLIP>
+__device__ __forceinline__ void plan_apply_ptrs_var_wave(const PlanPtrsVarArgs& a, const uint64_t* __restrict__ dptrs,
+                                                         const uint64_t* __restrict__ pptrs,
+                                                         const int32_t* __restrict__ lens,
+                                                         const int32_t* __restrict__ glen,
+                                                         const uint8_t* __restrict__ plan,
+                                                         const int32_t* __restrict__ culprit) {
     const int lane = threadIdx.x & 63;
     uint64_t g;
     uint32_t slab;
@@ -348,16 +391,54 @@ __global__ void __launch_bounds__(256) k_plan_apply_ptrs_var(PlanPtrsVarArgs a, 
         cut |= used[q] && eff[q] < reach;
     }
     const bool aligned = __ballot(low) == 0;
-    const bool full = __ballot(cut) == 0;
     auto row = [&](uint32_t s) -> uint8_t* { return as_out(entry_of<NP>(p, s)); };
     auto len_of = [&](uint32_t s) -> uint32_t { return entry_of<NP>(eff, s); };
-    run_slab_var<16>(
-        v, L, slab, lane, aligned,
-        [&](uint32_t off) {
-            if (full) plan_column<true>(pw, PL, t256, k, n, t, row, (uint64_t)off);
-            else plan_column_var<true>(pw, PL, t256, k, n, t, row, len_of, off);
-        },
-        [&](uint32_t b) { plan_column_var<false>(pw, PL, t256, k, n, t, row, len_of, b); });
+    if constexpr (CLIP) {
+        const int32_t c = culprit[g];  // a scalar load
+        uint32_t cul = ~0u, own = L;
+        if (c >= 0 && c < k) {
+            cul = (uint32_t)c;
+            own = std::min(len_of(cul), L);
+        }
+        const bool full = __ballot(cut) == 0 && own >= reach;
+        auto of = [&](uint32_t l) -> uint32_t { return l == cul ? own : L; };
+        const ClippedRoom<decltype(of)> room{of};
+        run_slab_var<16>(
+            v, L, slab, lane, aligned,
+            [&](uint32_t off) {
+                if (full) plan_column<true>(pw, PL, t256, k, n, t, row, (uint64_t)off);
+                else plan_column_var<true>(pw, PL, t256, k, n, t, row, len_of, off, room);
+            },
+            [&](uint32_t b) { plan_column_var<false>(pw, PL, t256, k, n, t, row, len_of, b, room); });
+    } else {
+        const bool full = __ballot(cut) == 0;
+        run_slab_var<16>(
+            v, L, slab, lane, aligned,
+            [&](uint32_t off) {
+                if (full) plan_column<true>(pw, PL, t256, k, n, t, row, (uint64_t)off);
+                else plan_column_var<true>(pw, PL, t256, k, n, t, row, len_of, off);
+            },
+            [&](uint32_t b) { plan_column_var<false>(pw, PL, t256, k, n, t, row, len_of, b); });
+    }
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) k_plan_apply_ptrs_var(PlanPtrsVarArgs a, const uint64_t* __restrict__ dptrs,
+                                                             const uint64_t* __restrict__ pptrs,
+                                                             const int32_t* __restrict__ lens,
+                                                             const int32_t* __restrict__ glen,
+                                                             const uint8_t* __restrict__ plan) {
+    plan_apply_ptrs_var_wave<NP, false>(a, dptrs, pptrs, lens, glen, plan, nullptr);
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) k_plan_apply_ptrs_var_clip(PlanPtrsVarArgs a, const uint64_t* __restrict__ dptrs,
+                                                                  const uint64_t* __restrict__ pptrs,
+                                                                  const int32_t* __restrict__ lens,
+                                                                  const int32_t* __restrict__ glen,
+                                                                  const uint8_t* __restrict__ plan,
+                                                                  const int32_t* __restrict__ culprit) {
+    plan_apply_ptrs_var_wave<NP, true>(a, dptrs, pptrs, lens, glen, plan, culprit);
 }
 
 hipError_t launch_plan_build(const PlanBuildArgs& a, hipStream_t stream) {
@@ -405,6 +486,26 @@ hipError_t launch_plan_apply_ptrs_var(const PlanPtrsVarArgs& a, hipStream_t stre
     else
         hipLaunchKernelGGL((k_plan_apply_ptrs_var<4>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs, a.lens,
                            a.group_len, a.p.plan);
+    return hipGetLastError();
+}
+
+// culprit: [groups] of this launch, never NULL
+hipError_t launch_plan_apply_ptrs_var_clip(const PlanPtrsVarArgs& a, const int32_t* culprit, hipStream_t stream) {
+    if (a.p.groups == 0) return hipSuccess;
+    const uint64_t waves = a.p.groups * (uint64_t)a.p.wpg;
+    const int n = a.p.k + a.p.m;
+    if (a.p.wpg != ptrs_geom((int)a.p.block, 16).wpg || waves * 64u > (uint64_t)kMaxLaunchLanes || n > 256 || !culprit)
+        return hipErrorInvalidValue;  // caller chunks
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (n <= 64)
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var_clip<1>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs,
+                           a.lens, a.group_len, a.p.plan, culprit);
+    else if (n <= 128)
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var_clip<2>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs,
+                           a.lens, a.group_len, a.p.plan, culprit);
+    else
+        hipLaunchKernelGGL((k_plan_apply_ptrs_var_clip<4>), dim3(grid), dim3(256), 0, stream, a, a.p.dptrs, a.p.pptrs,
+                           a.lens, a.group_len, a.p.plan, culprit);
     return hipGetLastError();
 }
 

@@ -63,10 +63,11 @@ int run_wide_ptrs(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const ui
                        });
 }
 
-// the same with per-shard lengths: lens / glen are the chunk's parts of d_lens and d_group_len
+// the same with per-shard lengths: lens / glen are the chunk's parts of d_lens and d_group_len.  culprit
+// (the scrub's repair; else NULL): [gn], a data id there is written up to its own length only
 int run_plan_apply_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
                             const int32_t* lens, const int32_t* glen, const uint8_t* d_plan, long long gn, int max_len,
-                            unsigned* d_invalid, hipStream_t s) {
+                            unsigned* d_invalid, hipStream_t s, const int32_t* culprit) {
     PlanPtrsVarArgs a{};
     const PtrsGeom p = ptrs_geom(max_len, 16);
     a.p.t256 = ctx.d_t256;
@@ -86,7 +87,7 @@ int run_plan_apply_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint64_t* dpt
         a.lens = lens + (size_t)g0 * a.p.k;
         a.group_len = glen + g0;
         a.p.groups = (uint64_t)n;
-        const hipError_t e = launch_plan_apply_ptrs_var(a, s);
+        const hipError_t e = culprit ? launch_plan_apply_ptrs_var_clip(a, culprit + g0, s) : launch_plan_apply_ptrs_var(a, s);
         return e == hipSuccess ? QFEC_OK : hip_fail(e, "plan_apply_ptrs_var kernel launch");
     });
 }
@@ -94,12 +95,29 @@ int run_plan_apply_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint64_t* dpt
 static int run_wide_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint64_t* dptrs,
                              const uint64_t* pptrs, const int32_t* lens, const int32_t* glen, const uint8_t* dmarks,
                              const uint8_t* pmarks, long long gn, int max_len, int mode, unsigned* d_failed,
-                             unsigned* d_invalid, hipStream_t s, const char* who) {
+                             unsigned* d_invalid, hipStream_t s, const char* who, const int32_t* culprit = nullptr) {
     return wide_chunks(ctx, c, tab, dmarks, pmarks, gn, max_len, mode, d_failed, s, who,
                        [&](long long g0, long long n, const uint8_t* plan) {
                            return run_plan_apply_ptrs_var(ctx, c, dptrs + (size_t)g0 * c->k, pptrs + (size_t)g0 * c->m,
-                                                          lens + (size_t)g0 * c->k, glen + g0, plan, n, max_len, d_invalid, s);
+                                                          lens + (size_t)g0 * c->k, glen + g0, plan, n, max_len, d_invalid, s,
+                                                          culprit ? culprit + g0 : nullptr);
                        });
+}
+
+// qfec_scrub_ptrs_wide_var's repair: qfec_repair_ptrs_wide_var on the locate's marks (rs.c layout over
+// `groups`), the located data shard of a group written up to its own length only, the lengths not
+// counted (the locate judged them)
+int run_repair_ptrs_wide_var_clip(DevCtx& ctx, qfec_code* c, const uint64_t* t, const int32_t* lens, const int32_t* glen,
+                                  const uint8_t* marks, const int32_t* culprit, long long groups, int max_len,
+                                  unsigned* d_failed, hipStream_t s, const char* who) {
+    uint32_t* tab = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        const int rc = ensure_enc(c, ctx.device, &tab);
+        if (rc) return rc;
+    }
+    return run_wide_ptrs_var(ctx, c, tab, t, t + (size_t)groups * c->k, lens, glen, marks, marks + (size_t)groups * c->k,
+                             groups, max_len, QFEC_PLAN_REPAIR, d_failed, nullptr, s, who, culprit);
 }
 
 static const char* bad_ptrs_args(const qfec_code* code, long long groups, int block_size) {

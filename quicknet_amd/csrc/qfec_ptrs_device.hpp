@@ -1,6 +1,6 @@
 // qfec_ptrs_device.hpp -- what the kernels on tables of shard addresses share (qfec_ptrs.hip: encode,
 // reconstruct; qfec_ptrs_var.hip: the same with per-shard lengths; qfec_plan.hip: k_plan_apply_ptrs,
-// k_plan_apply_ptrs_var; qfec_check.hip: k_check_apply_ptrs): reading an address out of the lane that loaded it, saying that it is global
+// k_plan_apply_ptrs_var; qfec_check.hip: k_check_apply_ptrs, k_check_apply_ptrs_var): reading an address out of the lane that loaded it, saying that it is global
 // memory, a wave's share of its group's shards, the encode's vector body on row addresses, and for
 // the kernels with per-shard lengths a lane's length, the clipped column load and a wave's share of
 // a group that has its own length, the ragged column loads of the templated bodies, and for the integrity
@@ -109,7 +109,7 @@ __device__ __forceinline__ uint32_t lane_value32(uint32_t v, uint32_t l) {
 }
 
 // register s >> 6 of the lane s & 63: entry s of the group's table (s wave-uniform, below 64 * NP);
-// k_plan_apply_ptrs_var of qfec_plan.hip and k_check_apply_ptrs of qfec_check.hip
+// k_plan_apply_ptrs_var of qfec_plan.hip, k_check_apply_ptrs and k_check_apply_ptrs_var of qfec_check.hip
 template <int NP>
 __device__ __forceinline__ uint64_t entry_of(const uint64_t (&p)[NP], uint32_t s) {
     const uint32_t l = s & 63u, r = s >> 6;

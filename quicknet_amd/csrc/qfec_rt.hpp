@@ -309,7 +309,11 @@ int run_plan_apply_ptrs(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, 
 // the same where every data shard has its own length: lens + g0 * k and glen + g0 go with a launch as well
 int run_plan_apply_ptrs_var(DevCtx& ctx, const qfec_code* c, const uint64_t* dptrs, const uint64_t* pptrs,
                             const int32_t* lens, const int32_t* glen, const uint8_t* d_plan, long long gn, int max_len,
-                            unsigned* d_invalid, hipStream_t s);
+                            unsigned* d_invalid, hipStream_t s, const int32_t* culprit = nullptr);
+// qfec_scrub_ptrs_wide_var's repair (t: the table, marks: rs.c layout, culprit: [groups], all of the batch)
+int run_repair_ptrs_wide_var_clip(DevCtx& ctx, qfec_code* c, const uint64_t* t, const int32_t* lens, const int32_t* glen,
+                                  const uint8_t* marks, const int32_t* culprit, long long groups, int max_len,
+                                  unsigned* d_failed, hipStream_t s, const char* who);
 // build into stream-ordered scratch, apply, free, in chunks of at most kPlanScratchCap of plans
 int run_wide_ptrs(DevCtx& ctx, const qfec_code* c, const uint32_t* tab, const uint64_t* dptrs, const uint64_t* pptrs,
                   const uint8_t* dmarks, const uint8_t* pmarks, long long gn, int block, int mode, unsigned* d_failed,
