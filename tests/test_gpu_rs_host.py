@@ -10,6 +10,7 @@ import pytest
 
 import quicknet_amd as qa
 from quicknet_amd.synth import erasure_marks, marks_to_rs_layout, synth_bytes
+from rs_abi_common import knobs, ptr_array  # noqa: F401  (knobs is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,21 +21,6 @@ if not torch.cuda.is_available():
 DEV = torch.device("cuda:0")
 
 
-@pytest.fixture
-def knobs():
-    """Set knobs for one test and put back what was there before (qfec_tune_get)."""
-    saved = {}
-
-    def set_(key, value):
-        if key not in saved:
-            saved[key] = qa.tune_get(key)
-        qa.tune(key, value)
-
-    yield set_
-    for key, value in saved.items():
-        qa.tune(key, value)
-
-
 def scattered_rows(G, n, B, seed):
     """G * n separately allocated host rows of B bytes (not one contiguous batch), in a random order
     in memory; returns (rows, keepalive)."""
@@ -43,10 +29,6 @@ def scattered_rows(G, n, B, seed):
     order = rng.permutation(G * n)
     rows = [pool[order[i], 8 + (i % 3) * 8:8 + (i % 3) * 8 + B] for i in range(G * n)]
     return rows, pool
-
-
-def ptr_array(rows):
-    return (C.c_void_p * len(rows))(*[r.ctypes.data if isinstance(r, np.ndarray) else r.data_ptr() for r in rows])
 
 
 def mixed_marks(G, k, m, seed):

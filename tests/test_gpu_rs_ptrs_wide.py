@@ -13,6 +13,7 @@ import pytest
 
 import quicknet_amd as qa
 from quicknet_amd.synth import marks_to_rs_layout, synth_bytes
+from rs_abi_common import device_rows, fetch, knobs, ptr_array  # noqa: F401  (knobs is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +24,6 @@ if not torch.cuda.is_available():
 DEV = torch.device("cuda:0")
 SHAPES = [(20, 10, 1000, 7), (40, 8, 1400, 6)]
 shape_ids = [f"{k}-{m}-B{B}-G{G}" for k, m, B, G in SHAPES]
-
-
-@pytest.fixture
-def knobs():
-    """Set knobs for one test and put back what was there before (qfec_tune_get)."""
-    saved = {}
-
-    def set_(key, value):
-        if key not in saved:
-            saved[key] = qa.tune_get(key)
-        qa.tune(key, value)
-
-    yield set_
-    for key, value in saved.items():
-        qa.tune(key, value)
 
 
 def marks_for(G, k, m, seed):
@@ -53,23 +39,6 @@ def marks_for(G, k, m, seed):
     gm[2, :] = 0
     gm[2, [0, k - 1, k, k + 2]] = 1
     return gm
-
-
-def device_rows(host_rows):
-    """One torch tensor per row: separate allocations, so the array is not one contiguous batch."""
-    rows = [torch.from_numpy(np.ascontiguousarray(r)).to(DEV) for r in host_rows]
-    B = len(host_rows[0])
-    assert any(rows[i].data_ptr() != rows[0].data_ptr() + i * B for i in range(1, len(rows)))
-    return rows
-
-
-def ptr_array(rows):
-    return (C.c_void_p * len(rows))(*[r.data_ptr() for r in rows])
-
-
-def fetch(rows):
-    torch.cuda.synchronize()
-    return np.stack([r.cpu().numpy() for r in rows])
 
 
 def batch(k, m, B, G, seed, recoverable=False):
